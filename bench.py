@@ -1,4 +1,5 @@
-"""Benchmark: cell updates per second (GCUPS) of the hot path on MI355X, plus roofline and CPU baseline.
+"""Benchmark: cell updates per second (GCUPS) of the hot path on MI355X; with --full also reference legs and the CPU
+baseline.
 
 Workload (BASELINE.json metric "GCUPS at 65536^2 on 1 and 8 x MI355X", config 3 "65536^2 bit-packed
 board, 10k generations on one MI355X"): a 65536 x 65536 torus, splitmix random 50 % fill generated on the
@@ -7,16 +8,20 @@ device (data: synthetic).  One *step* = one pass of the streaming kernel that ad
 process per GPU under torchrun) the board is 65536 wide and 65536*N tall, split into N row strips of
 65536^2 cells with RCCL halo exchange (weak scaling: per-GPU work fixed).
 
-    python bench.py                          # N = 1: 10k generations timed (~0.5 s), under a minute in all
+    python bench.py                          # N = 1: 10k generations timed (~0.5 s): set up, warm up, time, print
     python bench.py --steps 64 --warmup 4 --tblock 16
-    torchrun --nproc-per-node 8 bench.py --gpus 8
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR   # and the last timed step's board as DIR/*.npy
+    python bench.py --full                   # and every other leg: self-check against the golden checkpoints, the
+                                             # one-process C-ABI board, K = 1 and copy reference points, CPU baselines
+    torchrun --nproc-per-node 8 bench.py --gpus 8 --full
     # BASELINE configs 2 and 5 on the C-ABI board (the product's pass choice), one gol_step call per step:
     python bench.py --init dotnet-mod2 --seed 42 --width 4096 --height 4096 --generations 1000 --steps 5
     python bench.py --init rle:gosper-gun@1000,1000+r-pentomino@3000,3000 --width 4096 --height 4096 \
         --generations 100000 --steps 1 --warmup 1
 
 Prints ONE JSON line (rank 0).  Inputs are resident in HBM before the timed region; the timed region is
-bracketed by barrier + device synchronize on both sides, max over ranks.
+bracketed by barrier + device synchronize on both sides, max over ranks.  A plain run does only what that line's
+headline figure needs; --no-verify, --no-cpu-baseline and --handle-parts 0 drop single legs of a --full run.
 """
 from __future__ import annotations
 
@@ -206,7 +211,78 @@ def parse():
     p.add_argument("--handle-transport", choices=["default", "rccl"], default="default", help=argparse.SUPPRESS)
     p.add_argument("--no-verify", action="store_true",
                    help="skip the untimed self-check (step to the next golden checkpoint and compare hashes)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run every other leg: the self-check against the golden checkpoints, "
+                   "the one-process C-ABI board (handle leg), the K = 1 and device-copy reference points, the N > 1 "
+                   "report's probe passes and the CPU baselines (default: only what the headline figure needs)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write the board the last timed step left, as a caller reads it back "
+                   "(cells 0/1), to DIR/<name>.npy: cells (float32; every row, or a fixed seeded sample of whole rows "
+                   "within DUMP_BUDGET_BYTES), rows (their board row numbers), generation, population and hash (the "
+                   "whole board's; hash as four 16-bit limbs, high first), float64.  The depth race is skipped (as "
+                   "--no-autotune), so the same arguments dump the same generation of the same board in every run")
     return p.parse_args()
+
+
+DUMP_BUDGET_BYTES = 48 << 20  # the float32 cells of a dump (the other arrays are a few KB): under 64 MB in all
+DUMP_SEED = 0xD0D0
+
+
+def dump_rows(width: int, height: int):
+    """(rows, cols) of a --dump-outputs sample: the board rows written (all of them when they fit DUMP_BUDGET_BYTES as
+    float32, else a fixed sample without replacement from numpy's frozen legacy generator seeded DUMP_SEED, ascending)
+    and how many leading columns of each (all, unless one row alone exceeds the budget)."""
+    import numpy as np
+
+    cols = min(width, DUMP_BUDGET_BYTES // 4)
+    n = max(1, DUMP_BUDGET_BYTES // (4 * cols))
+    if n >= height:
+        return np.arange(height, dtype=np.int64), cols
+    return np.sort(np.random.RandomState(DUMP_SEED).choice(height, size=n, replace=False)).astype(np.int64), cols
+
+
+def write_dump(path: str, suffix: str, rows, cells, generation=None, hash64=None, population=None) -> None:
+    """The .npy files of --dump-outputs: cells<suffix> / rows<suffix> (one pair per rank), and the whole board's
+    generation, population and hash (rank 0)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, f"cells{suffix}.npy"), np.ascontiguousarray(cells, dtype=np.float32))
+    np.save(os.path.join(path, f"rows{suffix}.npy"), np.asarray(rows, dtype=np.float64))
+    if generation is not None:
+        np.save(os.path.join(path, "generation.npy"), np.array([generation], dtype=np.float64))
+        np.save(os.path.join(path, "population.npy"), np.array([population], dtype=np.float64))
+        np.save(os.path.join(path, "hash.npy"),
+                np.array([(hash64 >> s) & 0xFFFF for s in (48, 32, 16, 0)], dtype=np.float64))
+
+
+def dump_strip_outputs(path: str, runner, rank: int, world: int) -> None:
+    """--dump-outputs of the main leg, right after the timed steps: this rank's share of the sampled rows of the board
+    the last timed pass wrote, unpacked on the device as StripRunner.get_cells does (gol_strip_unpack) and only the
+    sample copied to the host; the whole board's hash and population (every rank takes part in the reductions)."""
+    import ctypes
+
+    import torch
+    from gameoflifewithactors_amd._lib import check
+
+    g = runner.geom
+    rows, cols = dump_rows(g.width, g.height)
+    rows = rows[(rows >= g.y0) & (rows < g.y0 + g.rows)]
+    s = runner.compute_stream
+    strip = g.strip()
+    with torch.cuda.stream(s):
+        cells = torch.empty((g.rows, g.width), dtype=torch.uint8, device=runner.device)
+        check(runner.engine.lib.gol_strip_unpack(ctypes.byref(strip), runner.bufs[runner.cur].data_ptr(),
+                                                 cells.data_ptr(), g.width, 1, s.cuda_stream), "gol_strip_unpack")
+        owned = torch.as_tensor(rows - g.y0, device=runner.device)
+        sample = cells.index_select(0, owned)[:, :cols].to(torch.float32).cpu()
+        del cells
+    h, pop = runner.hash(), runner.population()
+    suffix = "" if world == 1 else f"_rank{rank}"
+    if rank == 0:
+        write_dump(path, suffix, rows, sample.numpy(), runner.generation, h, pop)
+    else:
+        write_dump(path, suffix, rows, sample.numpy())
 
 
 def _cpu_model() -> str:
@@ -459,6 +535,9 @@ def board_leg(args) -> dict:
         end_hash, pop = b.hash(), b.population()
         gens = steps * gps
         end_gen = b.generation
+        if args.dump_outputs:  # the board the last timed gol_step call left, as gol_get_cells returns it
+            rows, cols = dump_rows(W, H)
+            write_dump(args.dump_outputs, "", rows, b.get_cells()[rows][:, :cols], end_gen, end_hash, pop)
     name, case = checkpoints.board_case(W, H, boundary, args.init, args.seed)
     init_mark = checkpoints.initial_mark(case)
     verify = checkpoints.verdict(end_gen, end_hash, pop, checkpoints.at_generation(case, end_gen),
@@ -562,7 +641,7 @@ def main():
     # that are within a few percent of each other across MI355X boxes.
     if args.tblock:
         cands = [args.tblock]
-    elif not args.no_autotune:
+    elif not args.no_autotune and not args.dump_outputs:
         cands = AUTOTUNE.get(ilv, [kdef])
     else:
         cands = [kdef]
@@ -620,14 +699,17 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt, kernel_s = float(t[0]), float(t[1])
 
+    if args.dump_outputs:  # before any other leg advances the board
+        dump_strip_outputs(args.dump_outputs, runner, rank, world)
+
     # N > 1: the ranks, their GPUs, RCCL's view of the group and the main leg's per-rank halo figures, after the
     # timed region (every rank takes part)
-    multi = multi_gpu_report(runner, dev, args.dist_backend, host_group) if world > 1 else None
+    multi = multi_gpu_report(runner, dev, args.dist_backend, host_group) if args.full and world > 1 else None
 
     # Memory-side reference point, outside the timed region: the same board streamed by K = 1 passes (the
-    # halo-free streaming kernel), HIP events on the compute stream.  Single GPU only.
+    # halo-free streaming kernel), HIP events on the compute stream.  Single GPU only, --full.
     k1 = None
-    if world == 1 and k > 1:
+    if args.full and world == 1 and k > 1:
         e0 = torch.cuda.Event(enable_timing=True)
         e1 = torch.cuda.Event(enable_timing=True)
         runner.step_pass(1)
@@ -645,7 +727,7 @@ def main():
     # Measured device-to-device copy rate on this box (torch copy_ of 1 GiB, 512 MiB read + 512 MiB written
     # per copy), outside the timed region: the practical HBM ceiling the roofline fractions sit under.
     copy_gbs = None
-    if world == 1:
+    if args.full and world == 1:
         a_ = torch.empty(1 << 27, dtype=torch.int32, device="cuda")
         b_ = torch.empty_like(a_)
         b_.copy_(a_)
@@ -680,7 +762,7 @@ def main():
     verify_gen = -1
     expected, source = None, None
     got_hash = got_pop = None
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         cname, case = checkpoints.splitmix_case(W, H, boundary, args.seed)
         expected = checkpoints.next_checkpoint(case, runner.generation)
         source = f"tests/golden/golden_full.json[{cname}]" if expected else None
@@ -691,7 +773,7 @@ def main():
     runner.close()  # the main leg is done: its buffers go and its engine releases the library (_lib.unload-able)
 
     # One-process C-ABI leg (rank 0), after the main leg; the other ranks wait on a host barrier.
-    parts = args.handle_parts if args.handle_parts >= 0 else world
+    parts = (args.handle_parts if args.handle_parts >= 0 else world) if args.full else 0
     handle = None
     if parts >= 1:
         if world > 1:
@@ -773,7 +855,7 @@ def main():
             result["verify"] = verify
         if handle is not None:
             result["handle_leg"] = handle
-        if not args.no_cpu_baseline and world == 1:  # the CPU baseline is an N = 1 figure (rank 0 only)
+        if args.full and not args.no_cpu_baseline and world == 1:  # the CPU baseline is an N = 1 figure (rank 0 only)
             result["cpu_baseline"] = cpu_baseline(args)
         print(json.dumps(result), flush=True)
     if world > 1:

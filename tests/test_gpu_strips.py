@@ -119,7 +119,7 @@ def test_bench_two_ranks_over_gloo():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29613", os.path.join(root, "bench.py"), "--gpus", "2",
-           "--steps", "2", "--warmup", "1", "--height", "4096", "--dist-backend", "gloo", "--no-cpu-baseline"]
+           "--steps", "2", "--warmup", "1", "--height", "4096", "--dist-backend", "gloo", "--no-cpu-baseline", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=100, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -158,7 +158,7 @@ def test_bench_two_ranks_strong_scaling_form_over_gloo():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29617", os.path.join(root, "bench.py"), "--gpus", "2",
            "--steps", "2", "--warmup", "1", "--board", "16384", "--dist-backend", "gloo", "--no-cpu-baseline",
-           "--handle-parts", "0", "--no-verify"]
+           "--handle-parts", "0", "--no-verify", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=100, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -199,7 +199,7 @@ def test_bench_single_gpu_json_contract():
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "4", "--warmup", "1", "--height", "8192",
-           "--cpu-seconds", "1", "--cpu-c2", "128"]
+           "--cpu-seconds", "1", "--cpu-c2", "128", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=150, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -216,3 +216,52 @@ def test_bench_single_gpu_json_contract():
     assert cb["kind"] == "port" and cb["unit"] == "GCUPS" and cb["value"] > 0 and cb["cores"] >= 1 and cb["sample"]
     assert set(cb["c1_100x100_100gens"]["gcups_by_seed"]) == {"0", "1", "42"} and cb["fair_cpu"]["value"] > 0
     assert r["value_per_gpu"] == r["value"]
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_last_timed_board(tmp_path):
+    """bench.py without --full: the headline line only (no self-check, handle leg, reference points or CPU baseline),
+    and --dump-outputs writes the board the last timed pass left.  8192 x 2048 is larger than the dump's budget, so
+    the cells are the seeded sample of whole rows (bench.dump_rows); they, the hash and the population must be those
+    of the C-ABI board stepped from the same seed to the dumped generation."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    from gameoflifewithactors_amd import Board
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+
+    w, h, seed = 8192, 2048, 77
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--width", str(w), "--height", str(h), "--seed", str(seed), "--dump-outputs", str(tmp_path)]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=100, cwd=root)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout
+    r = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in r, key
+    assert r["steps"] == 3 and r["warmup"] == 1 and r["value"] > 0 and r["ms_per_step"] > 0
+    for key in ("verify", "handle_leg", "cpu_baseline", "multi_gpu"):
+        assert key not in r, key
+    assert r["roofline_k1_stream"] is None and r["hbm_copy_measured_gbs"] is None
+    assert r["config"]["tblock_autotune_us_per_gen"] is None  # no depth race: the dumped generation is fixed
+    gen = r["config"]["first_generation_timed"] + r["config"]["generations_timed"]
+    assert r["config"]["generations_timed"] == 3 * r["config"]["generations_per_step"]
+
+    got = {n[:-4]: np.load(tmp_path / n) for n in sorted(os.listdir(tmp_path))}
+    assert set(got) == {"cells", "rows", "generation", "population", "hash"}
+    assert got["cells"].dtype == np.float32 and all(got[n].dtype == np.float64 for n in got if n != "cells")
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    rows, cols = bench.dump_rows(w, h)
+    assert cols == w and 0 < len(rows) < h and np.array_equal(got["rows"], rows)
+    assert got["generation"].tolist() == [gen]
+    with Board(w, h) as b:
+        b.seed_splitmix(seed).step(gen)
+        want, want_hash, want_pop = b.get_cells(), b.hash(), b.population()
+    assert np.array_equal(got["cells"], want[rows].astype(np.float32))
+    assert got["population"].tolist() == [want_pop]
+    assert [int(x) for x in got["hash"]] == [(want_hash >> s) & 0xFFFF for s in (48, 32, 16, 0)]

@@ -51,6 +51,39 @@ def test_verdict():
     assert verdict(600, 5, 7)["ok"] is None
 
 
+def test_dump_rows_and_files(tmp_path):
+    """bench.py --dump-outputs: the row sample is fixed, ascending, without repeats and within the byte budget (every
+    row of a board that fits); the files are float32 cells and float64 for the rest, the 64-bit hash as 16-bit limbs."""
+    import sys
+
+    sys.path.insert(0, os.path.dirname(HERE))
+    import bench
+
+    rows, cols = bench.dump_rows(100, 100)
+    assert cols == 100 and np.array_equal(rows, np.arange(100))
+    for w, h in ((65536, 65536), (65536, 8 * 65536), (262144, 262144)):
+        rows, cols = bench.dump_rows(w, h)
+        assert cols == w and rows.dtype == np.int64 and len(rows) == bench.DUMP_BUDGET_BYTES // (4 * w)
+        assert np.all(np.diff(rows) > 0) and rows[0] >= 0 and rows[-1] < h
+        assert np.array_equal(rows, bench.dump_rows(w, h)[0])
+    rows, cols = bench.dump_rows(1 << 30, 4)  # one row alone is past the budget: its leading columns
+    assert len(rows) == 1 and 4 * cols == bench.DUMP_BUDGET_BYTES
+    assert bench.DUMP_BUDGET_BYTES + (1 << 20) <= 64 << 20
+
+    cells = (np.arange(12).reshape(3, 4) % 2).astype(np.uint8)
+    h64 = 0xFEDCBA9876543210
+    bench.write_dump(str(tmp_path), "", [1, 5, 9], cells, 96, h64, 6)
+    bench.write_dump(str(tmp_path), "_rank1", [11], cells[:1])
+    got = {n: np.load(tmp_path / n) for n in os.listdir(tmp_path)}
+    assert set(got) == {"cells.npy", "rows.npy", "generation.npy", "population.npy", "hash.npy", "cells_rank1.npy",
+                        "rows_rank1.npy"}
+    assert got["cells.npy"].dtype == np.float32 and np.array_equal(got["cells.npy"], cells)
+    assert all(a.dtype == np.float64 for n, a in got.items() if not n.startswith("cells"))
+    assert got["rows.npy"].tolist() == [1, 5, 9] and got["rows_rank1.npy"].tolist() == [11]
+    assert got["generation.npy"].tolist() == [96] and got["population.npy"].tolist() == [6]
+    assert sum(int(x) << s for x, s in zip(got["hash.npy"], (48, 32, 16, 0))) == h64
+
+
 def _free_port():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
