@@ -27,6 +27,21 @@ extern int gol_seed_dotnet(nativeint board, int seed, int mode)
 extern int gol_step(nativeint board, int64 generations)
 [<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
 extern int gol_render_gray8(nativeint board, byte[] pixels, int64 stride, byte aliveValue)
+/// gol_view: pixel (i, j) covers the Scale x Scale cells from (X + Scale*i, Y + Scale*j)
+[<Struct; StructLayout(LayoutKind.Sequential)>]
+type GolView =
+    val mutable X: int64
+    val mutable Y: int64
+    val mutable Scale: int64
+    val mutable OutW: int64
+    val mutable OutH: int64
+type ViewMode = Any = 0 | Density = 1            // GOL_VIEW_ANY | GOL_VIEW_DENSITY
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int gol_view_counts(nativeint board, GolView& view, uint32[] counts)   // counts.[i + j*OutW]
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int gol_render_view(nativeint board, GolView& view, int mode, byte aliveValue, byte[] pixels, int64 stride)
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern byte gol_view_tone(uint32 count, int64 scale, int mode, byte aliveValue)
 [<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
 extern int gol_save_packed(nativeint board, uint64[] words, int64 len)   // canonical snapshot, H*ceil(W/64)
 [<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
@@ -64,6 +79,16 @@ type Board(width: int, height: int, boundary: Boundary, ?numGpus: int) =
         check "gol_get_cells" (gol_get_cells(h, a, int64 a.Length)); a
     member _.Render(pixels: byte[], alive: byte) =
         check "gol_render_gray8" (gol_render_gray8(h, pixels, int64 width, alive))
+    /// Gray8 frame of a view (x, y, scale, outW, outH) into pixels.[i + j*outW]: the zoomed-out or panned picture
+    /// of a board too large to show cell by cell (GameOfLifeUI.fs:21-31 at one pixel per scale x scale cells).
+    member _.RenderView(x: int64, y: int64, scale: int64, outW: int, outH: int, mode: ViewMode, alive: byte,
+                        pixels: byte[]) =
+        let mutable v = GolView(X = x, Y = y, Scale = scale, OutW = int64 outW, OutH = int64 outH)
+        check "gol_render_view" (gol_render_view(h, &v, int mode, alive, pixels, int64 outW))
+    member _.ViewCounts(x: int64, y: int64, scale: int64, outW: int, outH: int) =
+        let mutable v = GolView(X = x, Y = y, Scale = scale, OutW = int64 outW, OutH = int64 outH)
+        let c = Array.zeroCreate<uint32> (outW * outH)
+        check "gol_view_counts" (gol_view_counts(h, &v, c)); c
     member _.Save() =   // 1 bit per cell, layout- and GPU-count-independent
         let w = Array.zeroCreate<uint64> (height * ((width + 63) / 64))
         check "gol_save_packed" (gol_save_packed(h, w, int64 w.Length)); w
@@ -86,3 +111,9 @@ type Board(width: int, height: int, boundary: Boundary, ?numGpus: int) =
         check "gol_transport" (gol_transport(h, &t, note, int64 note.Capacity)); (t, note.ToString())
     interface IDisposable with
         member _.Dispose() = if h <> 0n then (gol_destroy h |> ignore; h <- 0n)
+
+/// A new Gray8 frame (outW * outH bytes) of the view: what the render agent writes to its bitmap per tick.
+let renderView (board: Board) (x: int64, y: int64, scale: int64, outW: int, outH: int) (mode: ViewMode) (alive: byte) =
+    let pixels = Array.zeroCreate<byte> (outW * outH)
+    board.RenderView(x, y, scale, outW, outH, mode, alive, pixels)
+    pixels

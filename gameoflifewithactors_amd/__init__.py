@@ -9,13 +9,14 @@ applying B3/S23 every generation) with HIP kernels behind a C ABI (``include/gol
 * ``driver``          -- run() / update_view() / UpdateAgent (GameOfLifeDriver.fs, GameOfLifeUI.fs)
 * ``strips``          -- multi-GPU row strips with the halo exchange (one process per GPU)
 """
-from ._lib import BOUNDED, INIT_DOTNET_MOD2, INIT_DOTNET_NEXT2, TORUS, GolError  # noqa: F401
+from ._lib import (BOUNDED, INIT_DOTNET_MOD2, INIT_DOTNET_NEXT2, TORUS, VIEW_ANY, VIEW_DENSITY,  # noqa: F401
+                   GolError)
 
 __version__ = "0.1.0"
 
 
 def __getattr__(name):  # lazy: importing the package must not require the shared library
-    if name in ("Board", "hash_finalize"):
+    if name in ("Board", "hash_finalize", "view_tone"):
         from . import board
 
         return getattr(board, name)

@@ -61,6 +61,15 @@ class Strip(ctypes.Structure):
     ]
 
 
+class View(ctypes.Structure):
+    """``gol_view`` (include/gol/gol.h): pixel (i, j) covers the scale x scale cells from (x + scale*i, y + scale*j)."""
+
+    _fields_ = [("x", ctypes.c_int64), ("y", ctypes.c_int64), ("scale", ctypes.c_int64), ("out_w", ctypes.c_int64),
+                ("out_h", ctypes.c_int64)]
+
+
+VIEW_ANY, VIEW_DENSITY = 0, 1
+
 _lib = None
 # Objects that keep the loaded CDLL and may call it later (open Board handles, strips.HipEngine): unload() refuses
 # while any is alive, since a call through a dlclosed library jumps into unmapped code (ADVICE round 4)
@@ -86,6 +95,8 @@ i64p = ctypes.POINTER(ctypes.c_int64)
 u64p = ctypes.POINTER(ctypes.c_uint64)
 ip = ctypes.POINTER(ctypes.c_int)
 sp = ctypes.POINTER(Strip)
+viewp = ctypes.POINTER(View)
+u32p = ctypes.POINTER(ctypes.c_uint32)
 
 # name -> (restype, argtypes).  Must cover every function include/gol/gol.h declares.
 SIGNATURES = {
@@ -110,6 +121,10 @@ SIGNATURES = {
     "gol_generation": (ctypes.c_int, [vp, i64p]),
     "gol_synchronize": (ctypes.c_int, [vp]),
     "gol_render_gray8": (ctypes.c_int, [vp, u8p, i64, ctypes.c_uint8]),
+    "gol_view_counts": (ctypes.c_int, [vp, viewp, u32p]),
+    "gol_render_view": (ctypes.c_int, [vp, viewp, ctypes.c_int, ctypes.c_uint8, u8p, i64]),
+    "gol_view_tone": (ctypes.c_uint8, [ctypes.c_uint32, i64, ctypes.c_int, ctypes.c_uint8]),
+    "gol_strip_view_counts": (ctypes.c_int, [sp, vp, viewp, vp, vp]),
     "gol_population": (ctypes.c_int, [vp, i64p]),
     "gol_hash": (ctypes.c_int, [vp, u64p]),
     "gol_info": (ctypes.c_int, [vp, i64p, i64p, ip, ip, ip]),

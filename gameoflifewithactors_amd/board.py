@@ -13,9 +13,10 @@ import ctypes
 import numpy as np
 
 from . import _lib, patterns
-from ._lib import BOUNDED, INIT_DOTNET_MOD2, INIT_DOTNET_NEXT2, TORUS, check
+from ._lib import BOUNDED, INIT_DOTNET_MOD2, INIT_DOTNET_NEXT2, TORUS, VIEW_ANY, VIEW_DENSITY, check
 
-__all__ = ["Board", "TORUS", "BOUNDED", "INIT_DOTNET_MOD2", "INIT_DOTNET_NEXT2", "hash_finalize"]
+__all__ = ["Board", "TORUS", "BOUNDED", "INIT_DOTNET_MOD2", "INIT_DOTNET_NEXT2", "VIEW_ANY", "VIEW_DENSITY",
+           "hash_finalize", "view_tone"]
 
 
 def _u8p(a: np.ndarray):
@@ -24,6 +25,11 @@ def _u8p(a: np.ndarray):
 
 def hash_finalize(partial_sum: int, width: int, height: int) -> int:
     return int(_lib.load().gol_hash_finalize(partial_sum & 0xFFFFFFFFFFFFFFFF, width, height))
+
+
+def view_tone(count: int, scale: int, mode: int = VIEW_ANY, alive_value: int = 128) -> int:
+    """gol_view_tone: the Gray8 tone of a view pixel of scale x scale cells holding `count` live ones (host-only)."""
+    return int(_lib.load().gol_view_tone(count, scale, mode, alive_value))
 
 
 class Board:
@@ -100,6 +106,25 @@ class Board:
         stride = self.width if stride is None else stride
         out = np.empty(stride * self.height, dtype=np.uint8)
         check(self._lib.gol_render_gray8(self._h, _u8p(out), stride, alive_value), "gol_render_gray8")
+        return out
+
+    def view_counts(self, x: int, y: int, scale: int, out_w: int, out_h: int) -> np.ndarray:
+        """Live cells per pixel of a view (gol_view_counts): pixel (i, j) covers the scale x scale cells from
+        (x + scale*i, y + scale*j), wrapped on a torus, dead outside a bounded board.  (out_h, out_w) uint32."""
+        v = _lib.View(x, y, scale, out_w, out_h)
+        out = np.empty((max(out_h, 0), max(out_w, 0)), dtype=np.uint32)
+        check(self._lib.gol_view_counts(self._h, ctypes.byref(v), out.ctypes.data_as(_lib.u32p)), "gol_view_counts")
+        return out
+
+    def render_view(self, x: int, y: int, scale: int, out_w: int, out_h: int, mode: int = VIEW_ANY,
+                    alive_value: int = 128, stride: int | None = None) -> np.ndarray:
+        """Gray8 frame of a view (gol_render_view): VIEW_ANY lights a pixel when any of its cells lives, VIEW_DENSITY
+        scales alive_value by the live fraction.  (out_h, stride) uint8, zero between out_w and stride."""
+        stride = out_w if stride is None else stride
+        v = _lib.View(x, y, scale, out_w, out_h)
+        out = np.empty((max(out_h, 0), max(stride, 0)), dtype=np.uint8)
+        check(self._lib.gol_render_view(self._h, ctypes.byref(v), mode, alive_value, _u8p(out), stride),
+              "gol_render_view")
         return out
 
     # ---------------------------------------------------------------- seeding

@@ -19,6 +19,7 @@
 #include "gol_debug.h"
 #include "gol_internal.h"
 #include "gol_multi.h"
+#include "gol_view.h"
 
 namespace {
 
@@ -266,6 +267,8 @@ struct BoardOptions {
     bool coop_launch = false;                 // "coop_launch": persistent passes by hipLaunchCooperativeKernel (1), or
                                               // hipLaunchKernel after the same residency check (0, the default:
                                               // gol_internal.h launch_persistent)
+    bool view_stream = true;                  // "view_stream": wide-tile views on the streaming kernel (gol_view.hip);
+                                              // 0 = every view on the per-pixel kernel
 };
 
 struct gol_board {
@@ -885,6 +888,26 @@ int check_strip(const gol_strip* s) {
     return GOL_OK;
 }
 
+// A view of a width x height board (include/gol/gol.h gol_view): checked on the host, before any device work.
+int check_view(const gol_view* v, int64_t width, int64_t height, int boundary) {
+    if (!v) return fail(GOL_ERR_INVALID, "null view");
+    if (v->scale < 1 || v->scale > gol::kViewMaxScale) return fail(GOL_ERR_INVALID, "view scale must be 1..32768");
+    if (v->out_w < 1 || v->out_h < 1 || v->out_w > gol::kViewMaxPixels || v->out_h > gol::kViewMaxPixels ||
+        v->out_w * v->out_h > gol::kViewMaxPixels)
+        return fail(GOL_ERR_INVALID, "view needs out_w, out_h >= 1 and out_w * out_h <= 2^26");
+    if (boundary == GOL_TORUS) {
+        if (v->x < 0 || v->x >= width || v->y < 0 || v->y >= height)
+            return fail(GOL_ERR_INVALID, "torus view: the origin must lie on the board");
+        if (v->scale * v->out_w > width || v->scale * v->out_h > height)
+            return fail(GOL_ERR_INVALID, "torus view: scale * out_w / out_h exceeds the board (cells would count twice)");
+    } else {
+        const int64_t lim = (int64_t)1 << 31;
+        if (v->x < -lim || v->x > lim || v->y < -lim || v->y > lim)
+            return fail(GOL_ERR_INVALID, "bounded view: the origin must lie in [-2^31, 2^31]");
+    }
+    return GOL_OK;
+}
+
 // k = 16 / 32 at ilv 4 is the level-pipelined pass (gol_pipe.hip): torus strips with a full strip of blocks per row
 int check_pipe_strip(const gol_strip* s, int k) {
     if (s->ilv == 4 && gol::pipe_supported(k) &&
@@ -962,6 +985,19 @@ int strip_step_opts(const gol_strip* s, const uint32_t* src, uint32_t* dst, int 
     }
     gol::StreamArgs a = strip_args(s, out_begin, out_end, split_opt, seg_opt, seam_opt, split2_opt);
     GOL_HIP(gol::launch_stream_step(src, dst, a, k, s->boundary == GOL_BOUNDED, s->wrap_rows != 0, stream));
+    return GOL_OK;
+}
+
+// gol_strip_view_counts with a board's "view_stream" option (the multi board's launches)
+int strip_view_counts_opts(const gol_strip* s, const uint32_t* buf, const gol_view* v, uint32_t* dev_counts,
+                           hipStream_t stream, bool stream_kernel) {
+    if (int rc = check_strip(s)) return rc;
+    if (!buf || !dev_counts) return fail(GOL_ERR_INVALID, "null buffer");
+    if (int rc = check_view(v, s->width, s->height, s->boundary)) return rc;
+    const gol::ViewSource src{buf, s->ilv, s->width, s->height, s->pitch, s->y0, s->rows, s->ghost,
+                              s->boundary == GOL_TORUS};
+    const gol::ViewArgs a{v->x, v->y, v->scale, v->out_w, v->out_h};
+    GOL_HIP(gol::launch_view_counts(src, a, dev_counts, stream_kernel, stream));
     return GOL_OK;
 }
 
@@ -1249,6 +1285,75 @@ int gol_render_gray8(gol_board* b, uint8_t* pixels, int64_t stride, uint8_t aliv
     DeviceGuard dg(b->device);
     if (!pixels || stride < b->W) return fail(GOL_ERR_INVALID, "stride must be >= width");
     return readback_impl(b, pixels, stride, alive_value);
+}
+
+uint8_t gol_view_tone(uint32_t count, int64_t scale, int mode, uint8_t alive_value) {
+    return gol::view_tone(count, scale, mode, alive_value);
+}
+
+// The counts of a view, and with pixels != null their tone map (out_h * stride bytes): one device buffer of counts is
+// zeroed, every rectangle of the view adds into it on the board's stream, and only the result crosses to the host.
+static int view_impl(gol_board* b, const gol_view* v, uint32_t* counts, int mode, uint8_t alive_value, uint8_t* pixels,
+                     int64_t stride) {
+    const int64_t n = v->out_w * v->out_h;
+    if (b->multi) {
+        if (!pixels) return b->multi->view_counts(v, counts, b->opt.view_stream);
+        std::vector<uint32_t> host((size_t)n);
+        if (int rc = b->multi->view_counts(v, host.data(), b->opt.view_stream)) return rc;
+        for (int64_t j = 0; j < v->out_h; j++) {
+            uint8_t* row = pixels + j * stride;
+            for (int64_t i = 0; i < v->out_w; i++)
+                row[i] = gol::view_tone(host[(size_t)(i + j * v->out_w)], v->scale, mode, alive_value);
+            std::memset(row + v->out_w, 0, (size_t)(stride - v->out_w));
+        }
+        return GOL_OK;
+    }
+    if (int rc = sync_bytes(b)) return rc;  // a ragged board's current generation may live in its scratch rows
+    const size_t npix = pixels ? (size_t)(v->out_h * stride) : 0;
+    uint32_t* dev = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&dev), (size_t)n * sizeof(uint32_t) + npix);
+    if (e != hipSuccess) return fail(GOL_ERR_OOM, std::string("hipMalloc view: ") + hipGetErrorString(e));
+    uint8_t* dev_pixels = reinterpret_cast<uint8_t*>(dev + n);
+    do {
+        e = hipMemsetAsync(dev, 0, (size_t)n * sizeof(uint32_t) + (stride != v->out_w ? npix : 0), b->stream);
+        if (e != hipSuccess) break;
+        const gol::ViewSource src{b->buf[b->cur], b->packed ? b->ilv : 0, b->W, b->H, b->packed ? b->pitch : b->W, 0,
+                                  b->H, 0, b->boundary == GOL_TORUS};
+        const gol::ViewArgs a{v->x, v->y, v->scale, v->out_w, v->out_h};
+        e = gol::launch_view_counts(src, a, dev, b->opt.view_stream, b->stream);
+        if (e != hipSuccess) break;
+        if (pixels) {
+            e = gol::launch_view_tone(dev, dev_pixels, v->out_w, v->out_h, stride, v->scale, mode, alive_value, b->stream);
+            if (e != hipSuccess) break;
+            e = hipMemcpyAsync(pixels, dev_pixels, npix, hipMemcpyDeviceToHost, b->stream);
+        } else {
+            e = hipMemcpyAsync(counts, dev, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream);
+        }
+        if (e != hipSuccess) break;
+        e = hipStreamSynchronize(b->stream);
+    } while (0);
+    (void)hipFree(dev);
+    if (e != hipSuccess) return fail(GOL_ERR_HIP, std::string("view: ") + hipGetErrorString(e));
+    return check_valid(b);
+}
+
+int gol_view_counts(gol_board* b, const gol_view* v, uint32_t* counts) {
+    if (int rc = check_board(b)) return rc;
+    std::lock_guard<std::mutex> g(b->mu);
+    if (int rc = check_view(v, b->W, b->H, b->boundary)) return rc;
+    if (!counts) return fail(GOL_ERR_INVALID, "null counts");
+    DeviceGuard dg(b->device);
+    return view_impl(b, v, counts, GOL_VIEW_ANY, 0, nullptr, 0);
+}
+
+int gol_render_view(gol_board* b, const gol_view* v, int mode, uint8_t alive_value, uint8_t* pixels, int64_t stride) {
+    if (int rc = check_board(b)) return rc;
+    std::lock_guard<std::mutex> g(b->mu);
+    if (int rc = check_view(v, b->W, b->H, b->boundary)) return rc;
+    if (mode != GOL_VIEW_ANY && mode != GOL_VIEW_DENSITY) return fail(GOL_ERR_INVALID, "view mode must be GOL_VIEW_ANY or GOL_VIEW_DENSITY");
+    if (!pixels || stride < v->out_w) return fail(GOL_ERR_INVALID, "stride must be >= out_w");
+    DeviceGuard dg(b->device);
+    return view_impl(b, v, nullptr, mode, alive_value, pixels, stride);
 }
 
 int gol_save_packed(gol_board* b, uint64_t* words, int64_t len) {
@@ -1543,7 +1648,8 @@ int gol_set_option(gol_board* b, const char* name, int64_t value) {
         if (value != 0 && value != 3 && value != 5 && value != 9 && value != 17)
             return fail(GOL_ERR_INVALID, "lanes_m must be 0, 3, 5, 9 or 17");
         o.lanes_m = (int)value;
-    } else if (is_debug_option(n))
+    } else if (n == "view_stream") o.view_stream = value != 0;
+    else if (is_debug_option(n))
         return fail(GOL_ERR_INVALID, "'" + n + "' is a test knob (gol_debug_set_option, csrc/gol_debug.h), not a board option");
     else
         return fail(GOL_ERR_INVALID, "unknown option '" + n + "'");
@@ -1633,6 +1739,7 @@ int gol_get_option(gol_board* b, const char* name, int64_t* value) {
     else if (n == "coop_poll_delay") *value = o.coop_poll_delay;
     else if (n == "lanes") *value = o.lanes;
     else if (n == "lanes_m") *value = o.lanes_m;
+    else if (n == "view_stream") *value = o.view_stream;
     else if (n == "transport") *value = b->multi ? b->multi->transport() : GOL_TRANSPORT_NONE;
     else if (is_debug_option(n))
         return fail(GOL_ERR_INVALID, "'" + n + "' is a test knob (gol_debug_get_option, csrc/gol_debug.h), not a board option");
@@ -1777,6 +1884,11 @@ int gol_strip_population(const gol_strip* s, const uint32_t* buf, uint64_t* dev_
     GOL_HIP(gol::launch_popcount_packed(buf, s->width / 32, s->rows, s->pitch, s->ghost,
                                         (unsigned long long*)dev_acc, (hipStream_t)stream));
     return GOL_OK;
+}
+
+int gol_strip_view_counts(const gol_strip* s, const uint32_t* buf, const gol_view* v, uint32_t* dev_counts,
+                          void* stream) {
+    return gol::strip_view_counts_opts(s, buf, v, dev_counts, (hipStream_t)stream, true);
 }
 
 int gol_strip_hash_partial(const gol_strip* s, const uint32_t* buf, uint64_t* dev_acc, void* stream) {

@@ -144,6 +144,28 @@ hipError_t launch_import_canonical(const uint64_t* in, int64_t W, int64_t rows, 
 hipError_t launch_set_points(void* board, int ilv, int64_t W, int64_t pitch, const int64_t* xy, int64_t n,
                              hipStream_t s);
 
+// ---- gol_view.hip: live-cell counts of the scale x scale pixels of a board view (gol_view_counts)
+struct ViewSource {
+    const void* base;  // buffer row 0: 32-bit words of layout ilv, or one byte per cell (ilv 0)
+    int ilv;           // words per interleaved block, 0 = byte board
+    int64_t W, H;      // the whole board
+    int64_t pitch;     // words per buffer row (byte boards: W cells)
+    int64_t y0, rows;  // the buffer's owned rows are the board's rows [y0, y0 + rows)
+    int64_t row0;      // buffer row of owned row 0 (a strip's ghost rows)
+    bool torus;
+};
+struct ViewArgs {
+    int64_t x, y, s, out_w, out_h;  // validated by the caller (gol_capi.cpp check_view)
+};
+// ADDS the counts of the owned rows into counts[out_w * out_h] (one launch per non-wrapping rectangle of the view:
+// up to four on a torus).  stream_kernel: wide tiles of packed boards (s >= 16 ilv; two tiles per word from 32 ilv, three
+// below) take the streaming kernel; otherwise, and for every other view, the per-pixel kernel.
+hipError_t launch_view_counts(const ViewSource& src, const ViewArgs& v, uint32_t* counts, bool stream_kernel,
+                              hipStream_t s);
+// pixels[i + j * stride] = view_tone(counts[i + j * out_w], scale, mode, alive_value) (gol_view.h)
+hipError_t launch_view_tone(const uint32_t* counts, uint8_t* pixels, int64_t out_w, int64_t out_h, int64_t stride,
+                            int64_t scale, int mode, uint8_t alive_value, hipStream_t s);
+
 // ---- gol_resident.hip: whole board in one workgroup's LDS, all generations in one launch
 bool resident_packed_fits(int64_t W, int64_t H);  // ilv = 1 layout
 bool resident_bytes_fits(int64_t W, int64_t H);

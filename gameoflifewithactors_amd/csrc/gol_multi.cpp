@@ -371,6 +371,31 @@ int MultiBoard::reduce(bool hash, uint64_t* out) {
     return GOL_OK;
 }
 
+int MultiBoard::view_counts(const gol_view* v, uint32_t* counts, bool stream_kernel) {
+    const size_t n = (size_t)(v->out_w * v->out_h);
+    std::fill(counts, counts + n, 0u);
+    // the parts whose owned rows the view can meet launch first, each on its own device and stream ...
+    std::vector<std::vector<uint32_t>> host(parts_.size());
+    std::vector<Staging> dev(parts_.size());  // freed (hipFree drains the device) before the host buffers go
+    for (size_t i = 0; i < parts_.size(); i++) {
+        Part& p = parts_[i];
+        GOL_MHIP(hipSetDevice(p.device));
+        GOL_MRC(dev[i].alloc(n * sizeof(uint32_t)));
+        host[i].resize(n);
+        GOL_MHIP(hipMemsetAsync(dev[i].p, 0, n * sizeof(uint32_t), p.compute));
+        GOL_MRC(strip_view_counts_opts(&p.s, p.buf[cur_], v, static_cast<uint32_t*>(dev[i].p), p.compute,
+                                       stream_kernel));
+        GOL_MHIP(hipMemcpyAsync(host[i].data(), dev[i].p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, p.compute));
+    }
+    // ... then the host adds the partials (tiles that straddle two strips get a share from each)
+    for (size_t i = 0; i < parts_.size(); i++) {
+        GOL_MHIP(hipSetDevice(parts_[i].device));
+        GOL_MHIP(hipStreamSynchronize(parts_[i].compute));
+        for (size_t k = 0; k < n; k++) counts[k] += host[i][k];
+    }
+    return GOL_OK;
+}
+
 // One pass of k generations over every part (the ordering argument is in DESIGN.md 5):
 //   compute[i]: record ev_start (previous pass of part i complete: compute joined edge at its end)
 //   copy[i]:    wait ev_start[i]; top k owned rows -> up's bottom ghost, bottom k -> down's top ghost;

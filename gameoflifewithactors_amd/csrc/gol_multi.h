@@ -34,6 +34,10 @@ int strip_step_opts(const gol_strip* s, const uint32_t* src, uint32_t* dst, int 
 int strip_plan_opts(const gol_strip* s, int k, int64_t out_begin, int64_t out_end, int64_t* waves, int64_t* seg_rows,
                     int32_t split_opt, int64_t seg_opt, int32_t seam_opt, int32_t split2_opt = 0);
 
+// gol_strip_view_counts with a board's "view_stream" option (gol_capi.cpp)
+int strip_view_counts_opts(const gol_strip* s, const uint32_t* buf, const gol_view* v, uint32_t* dev_counts,
+                           hipStream_t stream, bool stream_kernel);
+
 // The halo messages of one pass, in the order each part issues them (include/gol/gol.h gol_xfer): part r sends its
 // top k owned rows to `up` and its bottom k rows to `down`, then receives the down neighbour's top rows below its
 // owned rows and the up neighbour's bottom rows above them.  RCCL pairs a sender's sends to one peer with that
@@ -70,6 +74,9 @@ class MultiBoard {
     // step() between HIP events on every part's compute stream; *elapsed_us = the longest part's span (gol_step_timed)
     int step_timed(int64_t generations, int64_t* done, double* elapsed_us);
     int reduce(bool hash, uint64_t* out);
+    // gol_view_counts: every part adds the counts of its owned rows into a buffer on its own device (the strip
+    // primitive, on its compute stream); the host adds the parts' buffers into counts[out_w * out_h]
+    int view_counts(const gol_view* v, uint32_t* counts, bool stream_kernel);
     int synchronize();
     // one pass of the board's depth with timing events (gol_pass_timing): per part, microseconds from the
     // pass start to the interior launch's end, to the edge stream's release (halo copies landed) and to the

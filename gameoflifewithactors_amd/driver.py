@@ -7,7 +7,8 @@
 The cell actors and their 18 messages per cell per generation are replaced by one ``Board`` (HBM,
 HIP kernels).  ``update_view()`` keeps the reference's observable contract: it posts
 ``UpdateView.Reset`` and then one ``Update(alive, {x; y})`` per cell in ``applyGrid`` order -- or, with
-``emit="pixels"``, hands the agent the frame rendered on the GPU (``gol_render_gray8``).
+``emit="pixels"``, hands the agent the frame rendered on the GPU (``gol_render_gray8``); with ``emit="view"`` the
+frame is a zoomed or panned view of the board (``gol_render_view``: one pixel per scale x scale cells).
 """
 from __future__ import annotations
 
@@ -18,7 +19,7 @@ from typing import Callable, Optional
 
 import numpy as np
 
-from .board import INIT_DOTNET_MOD2, TORUS, Board
+from .board import INIT_DOTNET_MOD2, TORUS, VIEW_ANY, Board
 from .logic import Grid, Location, UpdateView, grid
 
 
@@ -59,10 +60,13 @@ class UpdateAgent:
 class GameOfLife:
     """The object ``run()`` returns: owns the board, the agent and the optional timer (IDisposable)."""
 
-    def __init__(self, board: Board, agent: UpdateAgent, emit: str):
-        if emit not in ("updates", "pixels"):
-            raise ValueError("emit must be 'updates' or 'pixels'")
+    def __init__(self, board: Board, agent: UpdateAgent, emit: str, view=None, view_mode: int = VIEW_ANY):
+        if emit not in ("updates", "pixels", "view"):
+            raise ValueError("emit must be 'updates', 'pixels' or 'view'")
+        if emit == "view" and (view is None or len(view) != 5):
+            raise ValueError("emit='view' needs view=(x, y, scale, out_w, out_h)")
         self.board, self.agent, self.emit = board, agent, emit
+        self.view, self.view_mode = (tuple(int(t) for t in view) if view is not None else None), view_mode
         self._timer: Optional[threading.Thread] = None
         self._stop = threading.Event()
         self._lock = threading.Lock()  # the reference's timer may re-enter updateView; serialise ticks
@@ -74,6 +78,10 @@ class GameOfLife:
             self.board.step(1)
             if self.emit == "pixels":
                 self.agent.post_frame(self.board.render_gray8(self.agent.alive_value))
+                return
+            if self.emit == "view":  # out_w * out_h pixels, pixels[i + j*out_w], of scale x scale cells each
+                frame = self.board.render_view(*self.view, mode=self.view_mode, alive_value=self.agent.alive_value)
+                self.agent.post_frame(frame.reshape(-1))
                 return
             cells = self.board.get_cells()
             g = self.agent.grid
@@ -115,17 +123,25 @@ def run(
     emit: str = "updates",
     tblock_k: int = 0,
     num_gpus: int = 1,
+    view=None,
+    view_mode: int = VIEW_ANY,
 ) -> GameOfLife:
     """GameOfLifeDriver.fs:13-41.  ``seed`` replaces ``int DateTime.Now.Ticks`` (L10) so runs are
     reproducible; the board is seeded x outer / y inner with ``Random.Next() % 2 = 0`` (L9-11,16-19).
     With ``period_s`` a timer ticks like L38-40 (reference: ProcessorCount * 70 ms).  ``num_gpus`` > 1
-    spreads the board over that many GPUs of this process (row strips; needs a width divisible by 32)."""
+    spreads the board over that many GPUs of this process (row strips; needs a width divisible by 32).
+    ``emit="view"`` posts one ``Board.render_view`` frame per tick for ``view = (x, y, scale, out_w, out_h)`` in
+    ``view_mode`` (VIEW_ANY / VIEW_DENSITY) instead of the whole board."""
     if seed is None:
         seed = int(time.time_ns() // 100) & 0xFFFFFFFF  # .NET ticks are 100 ns; `int` truncates to 32 bits
         seed = seed - (1 << 32) if seed >= (1 << 31) else seed
     board = Board(g.Width, g.Height, boundary, tblock_k, num_gpus=num_gpus)
     board.seed_dotnet(seed, INIT_DOTNET_MOD2)
-    game = GameOfLife(board, agent or UpdateAgent(g), emit)
+    try:
+        game = GameOfLife(board, agent or UpdateAgent(g), emit, view, view_mode)
+    except Exception:
+        board.close()
+        raise
     if period_s is not None:
         game.start(period_s)
     return game

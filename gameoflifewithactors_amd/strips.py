@@ -142,6 +142,19 @@ class HipEngine:
             check(fn(ctypes.byref(s), buf.data_ptr(), acc.data_ptr(), stream.cuda_stream), what)
         return acc
 
+    def view_counts(self, geom: Geometry, buf: torch.Tensor, view, counts: torch.Tensor, stream) -> None:
+        """gol_strip_view_counts: ADD the live-cell counts of this strip's owned rows for the view
+        (x, y, scale, out_w, out_h), in global board coordinates, into `counts` -- a contiguous int32 tensor of
+        out_h * out_w elements on this device that the caller zeroed (strips of one device may share it; across ranks
+        the caller sums the tensors).  Asynchronous on `stream`."""
+        x, y, scale, out_w, out_h = (int(t) for t in view)
+        if counts.dtype != torch.int32 or not counts.is_contiguous() or counts.numel() != out_w * out_h:
+            raise ValueError("counts must be a contiguous int32 tensor of out_w * out_h elements")
+        s = geom.strip()
+        v = _lib.View(x, y, scale, out_w, out_h)
+        check(self.lib.gol_strip_view_counts(ctypes.byref(s), buf.data_ptr(), ctypes.byref(v), counts.data_ptr(),
+                                             stream.cuda_stream), "gol_strip_view_counts")
+
     def set_cells(self, geom: Geometry, buf: torch.Tensor, cells_u8: torch.Tensor, stream) -> None:
         s = geom.strip()
         with torch.cuda.stream(stream):

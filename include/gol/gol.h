@@ -139,6 +139,34 @@ int gol_step_timed(gol_board* b, int64_t generations, double* elapsed_us);
  * pixels[x + y*stride] = alive ? alive_value : 0, stride >= width, buffer >= stride*height bytes. */
 int gol_render_gray8(gol_board* b, uint8_t* pixels, int64_t stride, uint8_t alive_value);
 
+/* A zoomable view of the board: what the render agent shows (GameOfLifeUI.fs:21-31) for boards no screen holds at one
+ * byte per cell.  Pixel (i, j) of a view covers the scale x scale cells (x + scale*i + a, y + scale*j + b),
+ * 0 <= a, b < scale; its count is the number of those cells that are alive.
+ *   GOL_TORUS:   coordinates wrap modulo width / height; 0 <= x < width, 0 <= y < height, scale*out_w <= width and
+ *                scale*out_h <= height (no cell is counted twice).
+ *   GOL_BOUNDED: cells outside the board are dead; x and y may be anything in [-2^31, 2^31], so a view may overhang
+ *                the board or lie wholly outside it.
+ *   Limits:      1 <= scale <= 32768 (a count fits uint32), out_w, out_h >= 1, out_w*out_h <= 2^26; anything else
+ *                returns GOL_ERR_INVALID before any device work.
+ * A view reads the board once and changes neither the board, its generation nor its hash; only the
+ * out_w*out_h counts (gol_view_counts) or out_h*stride bytes (gol_render_view) cross to the host.  Works on every
+ * layout, on byte boards and on multi-part boards. */
+typedef struct gol_view {
+    int64_t x, y, scale, out_w, out_h;
+} gol_view;
+enum { GOL_VIEW_ANY = 0, GOL_VIEW_DENSITY = 1 };
+/* counts[i + j*out_w] = live cells of pixel (i, j); host buffer of out_w*out_h uint32. */
+int gol_view_counts(gol_board* b, const gol_view* v, uint32_t* counts);
+/* pixels[i + j*stride] = gol_view_tone(count of pixel (i, j), scale, mode, alive_value); stride >= out_w, buffer >=
+ * stride*out_h bytes, the bytes between out_w and stride are set to 0.  With scale 1, x = y = 0 and out_w x out_h =
+ * width x height either mode gives the frame of gol_render_gray8. */
+int gol_render_view(gol_board* b, const gol_view* v, int mode, uint8_t alive_value, uint8_t* pixels, int64_t stride);
+/* Host-only, pure (like gol_hash_finalize): the Gray8 tone of a pixel of n = scale*scale cells.
+ *   GOL_VIEW_ANY:     count ? alive_value : 0
+ *   GOL_VIEW_DENSITY: (2*count*alive_value + n) / (2*n) in 64-bit integers (round half up)
+ * 0 for any other mode or a scale outside 1..32768. */
+uint8_t gol_view_tone(uint32_t count, int64_t scale, int mode, uint8_t alive_value);
+
 /* Observables for parity checks. */
 int gol_population(gol_board* b, int64_t* out);
 int gol_hash(gol_board* b, uint64_t* out); /* canonical 64-bit board hash */
@@ -201,6 +229,8 @@ int gol_pass_timing(gol_board* b, int n, double* interior_us, double* wait_us, d
  *                                measured faster (rows of <= 1024 cells), 1 = wherever it
  *                                applies, 0 = never
  *   "lanes_m" 0 | 3 | 5 | 9 | 17 its words per lane and half-row (0: 3 up to 1024 columns, else 9 when W % 512 == 0)
+ *   "view_stream" 1 | 0          views (gol_view_counts / gol_render_view) of packed boards with scale >= 16 * ilv on the
+ *                                streaming kernel (0: every view on the per-pixel kernel, the library's cross-check)
  * Unknown names and out-of-range values return GOL_ERR_INVALID.  Results are bit-identical for every setting.
  * (Test and A/B knobs -- spin limits, tag epochs, launch API -- are not board options: they live behind
  * gol_debug_set_option in the library's internal header csrc/gol_debug.h.)
@@ -255,6 +285,12 @@ int gol_strip_unpack(const gol_strip* s, const uint32_t* buf, uint8_t* dev_cells
 /* Add this strip's population / canonical-hash partial sum into *dev_acc (device uint64). */
 int gol_strip_population(const gol_strip* s, const uint32_t* buf, uint64_t* dev_acc, void* stream);
 int gol_strip_hash_partial(const gol_strip* s, const uint32_t* buf, uint64_t* dev_acc, void* stream);
+/* Row-strip primitive of gol_view_counts: ADDS the counts of this strip's OWNED rows (global rows [y0, y0+rows), never
+ * its ghost rows) into dev_counts[out_w*out_h] (device uint32; the caller zeroes it, and adds the strips' buffers when
+ * they live on different devices).  The view is in global board coordinates, with the rules of gol_view_counts for the
+ * strip's boundary.  Asynchronous on `stream`.  Arguments are validated before the device is touched. */
+int gol_strip_view_counts(const gol_strip* s, const uint32_t* buf, const gol_view* v, uint32_t* dev_counts,
+                          void* stream);
 /* Combine the (wrapping) sum of every strip's partial into the canonical board hash. */
 uint64_t gol_hash_finalize(uint64_t partial_sum, int64_t width, int64_t height);
 /* The halo messages of one pass of a multi-part board (one process, gol_create num_gpus > 1), in the order each

@@ -118,6 +118,18 @@ class Board {
         check(gol_render_gray8(b_, p.data(), w_, alive_value), "gol_render_gray8");
         return p;
     }
+    // A zoomed or panned view (gol.h gol_view): counts[i + j*out_w] live cells of pixel (i, j) ...
+    std::vector<uint32_t> viewCounts(const gol_view& v) const {
+        std::vector<uint32_t> c(v.out_w > 0 && v.out_h > 0 ? (size_t)(v.out_w * v.out_h) : 0);
+        check(gol_view_counts(b_, &v, c.data()), "gol_view_counts");
+        return c;
+    }
+    // ... and its Gray8 frame, pixels[i + j*out_w] (GOL_VIEW_ANY | GOL_VIEW_DENSITY)
+    std::vector<uint8_t> renderView(const gol_view& v, int mode = GOL_VIEW_ANY, uint8_t alive_value = 128) const {
+        std::vector<uint8_t> p(v.out_w > 0 && v.out_h > 0 ? (size_t)(v.out_w * v.out_h) : 0);
+        check(gol_render_view(b_, &v, mode, alive_value, p.data(), v.out_w), "gol_render_view");
+        return p;
+    }
     int64_t generation() const {
         int64_t g = 0;
         check(gol_generation(b_, &g), "gol_generation");
