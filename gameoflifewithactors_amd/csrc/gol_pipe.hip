@@ -11,7 +11,7 @@
 //   stage s     pushes each row through its D levels (the same level-fenced schedule as the streaming pass) and hands its
 //               level-(s + 1) D rows to stage s + 1 through a ring of LDS rows,
 //   stage S - 1 stores level K.
-// A wave's window is 5 D M = 80 VGPRs at (D, M) = (4, 4): 126 VGPRs in all, 4 waves per SIMD.  A pipeline streams its
+// A wave's window is 5 D M = 80 VGPRs at (D, M) = (4, 4): 122-124 VGPRs in all, 4 waves per SIMD.  A pipeline streams its
 // segment once, so the recomputed halo rows are one cone per pipeline (K (K - 1) level-rows), not one per wave.
 //
 // Ring protocol (per pipeline and stage boundary, no workgroup barrier): the producer writes output row j into slot
@@ -44,6 +44,7 @@
 #include <stdint.h>
 
 #include <atomic>
+#include <type_traits>
 #include <vector>
 
 #include "gol_bitlogic.h"
@@ -61,6 +62,7 @@ constexpr int kInterior = kWave - 2;  // blocks stored per full strip
 constexpr int kM = 4;                 // words per block (ilv 4)
 constexpr int kR = 4;                 // rows per trip
 constexpr int kNT = 2;                // trips per ring (NR = 8 rows)
+constexpr int kFillTrip = 0, kFullTrip = 1, kLastTrip = 2;  // a trip with nothing to hand on yet; with whole rows in and out; any
 constexpr int kNoStore = 0x7ffffff0;  // a lane offset past any row: its store is dropped by the range check
 constexpr int kRsrcWord3 = 0x00020000;
 constexpr int kWaitVm0 = 0x0F70;  // s_waitcnt vmcnt(0)
@@ -88,8 +90,11 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* p, int64_t by
 __device__ __forceinline__ uint32_t lds_addr(const void* p) {
     return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)p;
 }
-__device__ __forceinline__ void lds_publish(int* p, int v) {
-    asm volatile("ds_write_b32 %0, %1" : : "v"(lds_addr(p)), "v"(v) : "memory");
+// Every access names its LDS word or row as a per-wave base register plus an immediate OFF (bytes), so a trip spends
+// no VALU on addresses: the counters a stage touches lie within 24 bytes of one base, a trip's rows within 4 KB of one
+template <int OFF>
+__device__ __forceinline__ void lds_publish(uint32_t base, int v) {
+    asm volatile("ds_write_b32 %0, %1 offset:%2" : : "v"(base), "v"(v), "i"(OFF) : "memory");
 }
 #ifndef GOL_PIPE_SLEEP  // s_sleep periods (64 clocks) between polls
 #define GOL_PIPE_SLEEP 1
@@ -102,7 +107,8 @@ __device__ __forceinline__ void lds_publish(int* p, int v) {
 // loop put the head wherever the code before it ended, and the pass's speed followed that address by 25 % with an
 // 8-byte period (s_nop padding before the trip loop: 967-972 us per 65536^2 pass at an odd number of 4-byte nops,
 // 1196-1210 at an even one, profiles/r6/pipe/r6h)
-__device__ __forceinline__ int lds_wait(const int* p, int need, int limit) {
+template <int OFF>
+__device__ __forceinline__ int lds_wait(uint32_t base, int need, int limit) {
     int left = limit, tmp;
     asm volatile(
         "s_branch 2f\n"
@@ -113,27 +119,45 @@ __device__ __forceinline__ int lds_wait(const int* p, int need, int limit) {
         "s_cmp_le_i32 %[left], 0\n\t"
         "s_cbranch_scc1 3f\n"
         "2:\n\t"
-        "ds_read_b32 %[tmp], %[addr]\n\t"
+        "ds_read_b32 %[tmp], %[addr] offset:%[off]\n\t"
         "s_waitcnt lgkmcnt(0)\n\t"
         "v_cmp_gt_i32 vcc, %[need], %[tmp]\n\t"
         "s_cbranch_vccnz 1b\n"
         "3:"
         : [left] "+s"(left), [tmp] "=&v"(tmp)
-        : [addr] "v"(lds_addr(p)), [need] "s"(need)
+        : [addr] "v"(base), [need] "s"(need), [off] "i"(OFF)
         : "vcc", "scc", "memory");
     return left;
 }
-// four consecutive ring rows (one trip: 4 KB from `p`, lane-major 16 bytes per lane)
-__device__ __forceinline__ void lds_read_trip(const uint32_t* p, u32x4& r0, u32x4& r1, u32x4& r2, u32x4& r3) {
+// four consecutive rows (one trip: a 4 KB run from `base`, kRowBytes per row, lane-major 16 bytes per lane)
+constexpr int kRowBytes = kWave * kM * 4;
+__device__ __forceinline__ void lds_read_trip(uint32_t base, u32x4& r0, u32x4& r1, u32x4& r2, u32x4& r3) {
     asm volatile(
-        "ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:1024\n\tds_read_b128 %2, %4 offset:2048\n\t"
-        "ds_read_b128 %3, %4 offset:3072\n\ts_waitcnt lgkmcnt(0)"
+        "ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:%5\n\tds_read_b128 %2, %4 offset:%6\n\t"
+        "ds_read_b128 %3, %4 offset:%7\n\ts_waitcnt lgkmcnt(0)"
         : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(r3)
-        : "v"(lds_addr(p))
+        : "v"(base), "i"(kRowBytes), "i"(2 * kRowBytes), "i"(3 * kRowBytes)
         : "memory");
 }
-__device__ __forceinline__ void lds_write_row(uint32_t* p, const u32x4& w) {
-    asm volatile("ds_write_b128 %0, %1" : : "v"(lds_addr(p)), "v"(w) : "memory");
+// A level is 160 8-byte instructions back to back (v_bitop3, v_alignbit, DPP moves), and the pass's speed follows the
+// address they start at, modulo 8: this is the 25 % that once seemed to follow the poll loops' address (lds_wait).
+// Measured, not explained (profiles/pipe_trips/; addresses by llvm-objdump -d of the device object):
+//   levels starting at 4 (mod 8)  993-1004 us per 65536^2 torus pass  (GOL_PIPE_LEVEL_PAD 1, the default)
+//   levels starting at 0 (mod 8)  1235-1249 us                        (GOL_PIPE_LEVEL_PAD 0)
+// and the same on the parent's kernel with nothing but this pin added (1019-1023 against 1221-1255).  So every level
+// starts GOL_PIPE_LEVEL_PAD 4-byte nops past an 8-byte boundary, whatever code comes before it.  The pad is right for
+// the code this compiler emits (no 4-byte instruction at a level's head or inside it); DESIGN records the tally of
+// addresses a rebuild should reproduce -- if a compiler moves it, measure before touching the pad: the fast case is
+// the one OFF the boundaries.
+#ifndef GOL_PIPE_LEVEL_PAD
+#define GOL_PIPE_LEVEL_PAD 1
+#endif
+__device__ __forceinline__ void level_align() {
+    asm volatile(".p2align 3\n\t.rept " GOL_PIPE_STR(GOL_PIPE_LEVEL_PAD) "\n\ts_nop 0\n\t.endr");
+}
+template <int OFF>
+__device__ __forceinline__ void lds_write_row(uint32_t base, const u32x4& w) {
+    asm volatile("ds_write_b128 %0, %1 offset:%2" : : "v"(base), "v"(w), "i"(OFF) : "memory");
 }
 
 // A wave-uniform 64-bit value the compiler cannot prove uniform (float math), moved to SGPRs
@@ -203,8 +227,11 @@ template <int D, int S, int P, bool WRAP, bool BND>
 __global__ __launch_bounds__(kWave * S * P) __attribute__((amdgpu_waves_per_eu(S * P / 4)))
 void gol_pipe_step(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, PipeArgs a) {
     constexpr int K = D * S, NR = kNT * kR;
-    __shared__ __attribute__((aligned(16))) uint32_t dstage[P][2][kR][kWave * kM];         // stage 0: [par][row][lane][word]
-    __shared__ __attribute__((aligned(16))) uint32_t ring[P][S - 1][NR][kWave * kM];       // [slot][lane][word]
+    // both arrays are whole multiples of 8 KB and the only ones of that alignment, so they lie where they lay at 16;
+    // stating it lets a trip's 4 KB run change halves by one v_xor of its base
+    __shared__ __attribute__((aligned(2 * kR * kRowBytes))) uint32_t dstage[P][2][kR][kWave * kM];  // stage 0: [par][row][lane][word]
+    __shared__ __attribute__((aligned(2 * kR * kRowBytes))) uint32_t ring[P][S - 1][NR][kWave * kM];  // [slot][lane][word]
+    static_assert(kNT == 2 && 2 * D % kR == 0, "a ring of two trips; the fill ends on a trip boundary");
     __shared__ int ctr[P][S][2];                                                            // [0] rows out, [1] rows in
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -261,8 +288,15 @@ void gol_pipe_step(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst,
         delta = j < cnt ? (int64_t)j * a.grows * pitch_bytes : 0;
     }
     cb = cb < 0 ? cb + a.nblocks : (cb >= a.nblocks ? cb - a.nblocks : cb);
+    // A stage's counters lie within 24 bytes of one base: the producer's rows out (which stage 0 has none of), its own
+    // rows out and rows in, and the consumer's rows in
+    const uint32_t cbase = lds_addr(&ctr[p][s > 0 ? s - 1 : 0][0]);
+    // One register, `aux`, for what a stage needs in a vector register trip after trip: stage 0 loads at its lane's
+    // offset, the last stage stores there, and a stage between them has no such offset but twice the counter accesses,
+    // so it keeps the counters' base there (the end stages copy that from its scalar register at each use)
     const int load_off = (int)(cb * 4 * kM + delta);
-    const int store_off = stores ? load_off : kNoStore;
+    int aux = s == 0 ? load_off : (s == S - 1 ? (stores ? load_off : kNoStore) : (int)cbase);
+    asm volatile("" : "+v"(aux));  // (opaque: not to be taken apart again into its three sources)
     // bytes a row descriptor covers: the row, or (packed remainder) every sub-strip's row
     const int64_t span = (cnt > 1 ? (int64_t)(cnt - 1) * a.grows * pitch_bytes : 0) + a.words * 4;
     const int64_t buf_rows = WRAP ? a.rows : a.rows + 2 * a.ghost;
@@ -282,76 +316,100 @@ void gol_pipe_step(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst,
     } else {
         lrow = a.ghost + y0 - K;
     }
+    // the next row's address, moved on by a row's bytes per row (and wrapped or held as the row is): no multiply per row
+    const uint32_t* lptr = src + (WRAP ? lrow : (lrow < 0 ? 0 : (lrow < buf_rows ? lrow : buf_rows - 1))) * a.pitch;
     // bounded: the live rows [live_lo, live_hi) in buffer rows (32-bit scalars, as the clamp below)
     [[maybe_unused]] const int live_blo = (int)a.ghost + a.live_lo, live_bhi = (int)a.ghost + a.live_hi;
     auto dma_trip = [&](int par) {
 #pragma unroll
         for (int r = 0; r < kR; r++) {
-            int64_t br = lrow;
+            const uint32_t* row = lptr;
             bool dead = false;
             if (WRAP) {
-                lrow = lrow + 1 == a.rows ? 0 : lrow + 1;
+                const bool last = lrow + 1 == a.rows;
+                lrow = last ? 0 : lrow + 1;
+                lptr = last ? src : lptr + a.pitch;
             } else {
-                lrow++;
                 // 32-bit scalar compares (the buffer holds < 2^31 rows, pipe_check): the 64-bit clamp became VALU compares
                 // into VCC on stage 0's DMA issue, the pipeline's pacer
-                const int b32 = (int)br, n32 = (int)buf_rows;
-                br = b32 < 0 ? 0 : (b32 < n32 ? b32 : n32 - 1);
+                const int b32 = (int)lrow, n32 = (int)buf_rows;
+                lrow++;
+                lptr = b32 >= 0 && b32 < n32 - 1 ? lptr + a.pitch : lptr;  // rows clamped into the buffer: held at its ends
                 dead = BND && (b32 < live_blo || b32 >= live_bhi);  // a dead row: loads zeros
             }
             auto* q = (__attribute__((address_space(3))) void*)&dstage[p][par][r][0];
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc(src + br * a.pitch, dead ? 0 : span), q, 16, load_off, 0, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc(row, dead ? 0 : span), q, 16, aux, 0, 0, 0);
         }
     };
-    bool failed = false;
     const int spin_limit = (int)a.spin_limit;
-    auto wait_ge = [&](const int* c, int need) {
-        if (lds_wait(c, need, spin_limit) <= 0) {
+    constexpr int kCtr = 2 * (int)sizeof(int);  // a stage's pair of counters
+    constexpr int kFirstOut = 0, kFirstFree = kCtr + 4;                               // stage 0: ctr[0][0], ctr[1][1]
+    constexpr int kPrevOut = 0, kOut = kCtr, kIn = kCtr + 4, kNextFree = 2 * kCtr + 4;  // stage s: ctr[s - 1][0], ctr[s][0], ctr[s][1], ctr[s + 1][1]
+    auto wait_ge = [&](auto off, uint32_t cb, int need) __attribute__((always_inline)) {
+        // A wait that gives up ends the wave there and then.  A flag tested at each trip's end, as the single trip loop
+        // had, is merged under the lane-0 branch: it became a lane mask in a vector register, the loops' exits
+        // divergent, and whatever outlives a loop of trips -- the trip count, the row addresses -- vector values too.
+        // (The instruction is written out: to the compiler the path goes on, so the trips' control flow stays as it
+        // is without the wait; the builtin, which ends the path, cost 300 bytes of scratch.)
+        if (lds_wait<decltype(off)::value>(cb, need, spin_limit) <= 0) {
             if (lane == 0) __hip_atomic_fetch_or(a.err, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // vector atomic; bit 1: the pipeline
-            failed = true;
+            asm volatile("s_endpgm");
         }
     };
+    // A trip's rows in (stage 0: the staged rows, else the ring before this stage): one base register, its half
+    // alternating with the trip's parity.  Rows out trail rows in by 2D = NR rows, so they are in the same half of
+    // their ring, which lies a constant past the rows in: one ring for a later stage, `first_ring` for stage 0
+    uint32_t rd = s == 0 ? lds_addr(&dstage[p][0][0][lane * kM]) : lds_addr(&ring[p][s > 0 ? s - 1 : 0][0][lane * kM]);
+    const uint32_t first_ring = lds_addr(&ring[p][0][0][0]) - lds_addr(&dstage[p][0][0][0]);
+    constexpr int kRingBytes = NR * kRowBytes, kHalf = kR * kRowBytes;
+    static_assert(2 * D == NR, "rows out share the parity of rows in");
+    // the last stage's next row out
+    uint32_t* sptr = dst + ((WRAP ? 0 : a.ghost) + y0) * a.pitch;
 
-    uint32_t v[kR][kM];
-    if (s == 0) dma_trip(0);
-    for (int t = 0; t < T && !failed; t++) {
-        const int par = t & 1;
+    // One trip: rows kR t .. kR t + kR - 1 in, through D levels, rows kR t - 2D .. out.  The trips come in three kinds,
+    // each its own loop: the fill's (t < 2D / kR: whole rows in, nothing to hand on yet), the full ones (whole rows in
+    // and out, and another trip after them: no test of a row's range anywhere) and the last (any).
+    auto trip = [&](auto kind, const int t) __attribute__((always_inline)) {
+        constexpr bool FILL = decltype(kind)::value == kFillTrip, FULL = decltype(kind)::value != kLastTrip;
+        const int t4 = kR * t;
         // ---- inputs of trip t: rows kR t .. kR t + kR - 1
+        u32x4 x[kR];
+        const auto ring_in = [&](uint32_t cb) __attribute__((always_inline)) {
+            lds_publish<kIn>(cb, t4);  // trip t - 1's rows were read (and used)
+            wait_ge(std::integral_constant<int, kPrevOut>{}, cb, FULL || t4 + kR < n_in ? t4 + kR : n_in);
+            lds_read_trip(rd, x[0], x[1], x[2], x[3]);
+        };
         if (s == 0) {
             __builtin_amdgcn_s_waitcnt(kWaitVm0);
-#pragma unroll
-            for (int r = 0; r < kR; r++) {
-                const u32x4 x = *(const u32x4*)&dstage[p][par][r][lane * kM];
-                v[r][0] = x.x;
-                v[r][1] = x.y;
-                v[r][2] = x.z;
-                v[r][3] = x.w;
-            }
+            lds_read_trip(rd, x[0], x[1], x[2], x[3]);
             __builtin_amdgcn_sched_barrier(0);  // the reads before the next trip's DMAs overwrite the other parity
-            if (t + 1 < T) dma_trip(par ^ 1);
+            if (FULL || t + 1 < T) dma_trip((t & 1) ^ 1);
+        } else if (s == S - 1) {
+            ring_in(cbase);
         } else {
-            lds_publish(&ctr[p][s][1], kR * t);  // trip t - 1's rows were read (and used)
-            wait_ge(&ctr[p][s - 1][0], kR * t + kR < n_in ? kR * t + kR : n_in);
-            u32x4 x[kR];  // the trip's 4 rows: ring slots 4t .. 4t + 3 (mod NR = 8) are one 4 KB run
-            lds_read_trip(&ring[p][s - 1][(kR * t) % NR][lane * kM], x[0], x[1], x[2], x[3]);
+            ring_in((uint32_t)aux);
+        }
+        uint32_t v[kR][kM];
 #pragma unroll
-            for (int r = 0; r < kR; r++) {
-                v[r][0] = x[r].x;
-                v[r][1] = x[r].y;
-                v[r][2] = x[r].z;
-                v[r][3] = x[r].w;
-            }
+        for (int r = 0; r < kR; r++) {
+            v[r][0] = x[r].x;
+            v[r][1] = x[r].y;
+            v[r][2] = x[r].z;
+            v[r][3] = x[r].w;
         }
         __builtin_amdgcn_sched_barrier(0);
         // ---- D levels (the streaming pass's level-fenced schedule, gol_step.hip StreamWave::process): even row r takes
         // the window (X = row - 2, Y = row - 1) and leaves its sums in X, odd row r + 1 takes (Y, X)
         // bounded: this trip's rows, level by level: after level g, v[r] is row yt + r - g - 1 (owned-row coordinates),
         // over [yt - D, yt + kR - 2] in all; a trip reaching outside the live rows zeroes the rows it computes there
-        [[maybe_unused]] const int yt = (int)(y0 - K + s * D) + kR * t;
+        [[maybe_unused]] const int yt = (int)(y0 - K + s * D) + t4;
         [[maybe_unused]] const bool edge_trip = BND && (yt - D < a.live_lo || yt + kR - 2 >= a.live_hi);
         uint32_t right[kR];
 #pragma unroll
         for (int r = 0; r < kR; r++) right[r] = from_right<BND>(v[r][0]);
+        __builtin_amdgcn_sched_barrier(0);
+        level_align();
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int g = 0; g < D; g++) {
 #pragma unroll
@@ -395,30 +453,50 @@ void gol_pipe_step(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst,
                 }
             }
             __builtin_amdgcn_sched_barrier(0);  // level g + 1 may not be hoisted next to its exchanges
+            level_align();
+            __builtin_amdgcn_sched_barrier(0);
         }
         // ---- outputs: v[r] is this stage's output row j = kR t + r - 2D
-        const int j0 = kR * t - 2 * D;
-        if (s == S - 1) {
+        const int j0 = t4 - 2 * D;
+        const auto out = [&](int r) __attribute__((always_inline)) { return u32x4{v[r][0], v[r][1], v[r][2], v[r][3]}; };
+        if (FILL) {
+        } else if (s == S - 1) {
 #pragma unroll
             for (int r = 0; r < kR; r++) {
-                const int j = j0 + r;
-                const bool valid = j >= 0 && j < n_out;
-                const int64_t y = y0 + (valid ? j : 0);
-                const u32x4 w = {v[r][0], v[r][1], v[r][2], v[r][3]};
-                __builtin_amdgcn_raw_buffer_store_b128(w, rsrc(dst + ((WRAP ? 0 : a.ghost) + y) * a.pitch, valid ? span : 0),
-                                                       store_off, 0, 0);
+                const bool valid = FULL || (j0 + r >= 0 && j0 + r < n_out);
+                __builtin_amdgcn_raw_buffer_store_b128(out(r), rsrc(sptr, valid ? span : 0), aux, 0, 0);
+                sptr = valid ? sptr + a.pitch : sptr;
             }
-        } else if (j0 + kR > 0) {
-            const int jmax = j0 + kR - 1 < n_out - 1 ? j0 + kR - 1 : n_out - 1;
-            wait_ge(&ctr[p][s + 1][1], jmax + 1 - NR);  // the slots are free
-#pragma unroll
-            for (int r = 0; r < kR; r++) {
-                const int j = j0 + r;
-                if (j >= 0 && j < n_out) lds_write_row(&ring[p][s][j % NR][lane * kM], u32x4{v[r][0], v[r][1], v[r][2], v[r][3]});
+        } else if (FULL || j0 + kR > 0) {
+            const int jmax = FULL || j0 + kR - 1 < n_out - 1 ? j0 + kR - 1 : n_out - 1;
+            // the slots are free, then the rows, then the count of them
+            if (s == 0) {
+                const uint32_t wr0 = rd + first_ring;
+                wait_ge(std::integral_constant<int, kFirstFree>{}, cbase, jmax + 1 - NR);
+                if (FULL || (j0 + 0 >= 0 && j0 + 0 < n_out)) lds_write_row<0 * kRowBytes>(wr0, out(0));
+                if (FULL || (j0 + 1 >= 0 && j0 + 1 < n_out)) lds_write_row<1 * kRowBytes>(wr0, out(1));
+                if (FULL || (j0 + 2 >= 0 && j0 + 2 < n_out)) lds_write_row<2 * kRowBytes>(wr0, out(2));
+                if (FULL || (j0 + 3 >= 0 && j0 + 3 < n_out)) lds_write_row<3 * kRowBytes>(wr0, out(3));
+                lds_publish<kFirstOut>(cbase, jmax + 1);
+            } else {
+                wait_ge(std::integral_constant<int, kNextFree>{}, (uint32_t)aux, jmax + 1 - NR);
+                if (FULL || (j0 + 0 >= 0 && j0 + 0 < n_out)) lds_write_row<kRingBytes + 0 * kRowBytes>(rd, out(0));
+                if (FULL || (j0 + 1 >= 0 && j0 + 1 < n_out)) lds_write_row<kRingBytes + 1 * kRowBytes>(rd, out(1));
+                if (FULL || (j0 + 2 >= 0 && j0 + 2 < n_out)) lds_write_row<kRingBytes + 2 * kRowBytes>(rd, out(2));
+                if (FULL || (j0 + 3 >= 0 && j0 + 3 < n_out)) lds_write_row<kRingBytes + 3 * kRowBytes>(rd, out(3));
+                lds_publish<kOut>((uint32_t)aux, jmax + 1);
             }
-            lds_publish(&ctr[p][s][0], j0 + kR < n_out ? j0 + kR : n_out);
         }
-    }
+        rd ^= kHalf;  // the next trip's half
+    };
+
+    if (s == 0) dma_trip(0);
+    // n_in > 2D (L >= 1), so the fill's trips hold whole rows only and the last trip comes after them
+    constexpr int kFill = 2 * D / kR;
+    int t = 0;
+    for (; t < kFill; t++) trip(std::integral_constant<int, kFillTrip>{}, t);
+    for (; t < T - 1; t++) trip(std::integral_constant<int, kFullTrip>{}, t);
+    for (; t < T; t++) trip(std::integral_constant<int, kLastTrip>{}, t);
 }
 
 namespace {
