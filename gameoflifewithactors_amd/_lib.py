@@ -166,7 +166,7 @@ SIGNATURES = {
 # Names gol_debug_set_option / gol_debug_get_option take (csrc/gol_debug.h); Board.set_option routes them there.
 # The library exports its own list (gol_debug_option_names); tests/test_cpu_host.py checks this one against it.
 DEBUG_OPTIONS = frozenset({"coop_epoch", "coop_spin_limit", "coop_r", "resident_threads", "coop_launch",
-                           "lanes_launches"})
+                           "lanes_launches", "last_pass"})
 
 
 def _elf_sections(data: bytes, base: int = 0):

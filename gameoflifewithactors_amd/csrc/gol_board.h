@@ -1,0 +1,249 @@
+// gol_board.h -- what the host translation units of libgol_hip.so share (not installed): the board handle and its
+// options, the error return (fail, GOL_HIP), the RAII pieces of an entry point (DeviceGuard, DeviceBuffer, EventPair,
+// with_board) and the layout / pass policy's interface (gol_policy.cpp).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <exception>
+#include <mutex>
+#include <string>
+
+#include "../../include/gol/gol.h"
+#include "gol_internal.h"
+#include "gol_multi.h"
+
+namespace gol {
+
+// Sets gol_last_error (thread-local, gol_capi.cpp) and returns `code`.
+int api_fail(int code, const std::string& msg);
+inline int fail(int code, const std::string& msg) { return api_fail(code, msg); }
+
+#define GOL_HIP(expr)                                                                                       \
+    do {                                                                                                    \
+        hipError_t e_ = (expr);                                                                             \
+        if (e_ != hipSuccess) return gol::api_fail(GOL_ERR_HIP, std::string(#expr ": ") + hipGetErrorString(e_)); \
+    } while (0)
+#define GOL_RC(expr)                   \
+    do {                               \
+        int rc_ = (expr);              \
+        if (rc_ != GOL_OK) return rc_; \
+    } while (0)
+
+// Every board call runs on the board's device whatever device the calling thread has current (staging
+// buffers are allocated on the current device), and restores the caller's device afterwards.
+struct DeviceGuard {
+    int prev = -1;
+    explicit DeviceGuard(int dev) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (dev >= 0 && prev != dev) (void)hipSetDevice(dev);
+    }
+    ~DeviceGuard() {
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+};
+
+// Device memory of one call (staging), freed on every exit path.
+struct DeviceBuffer {
+    void* p = nullptr;
+    DeviceBuffer() = default;
+    DeviceBuffer(const DeviceBuffer&) = delete;
+    DeviceBuffer& operator=(const DeviceBuffer&) = delete;
+    ~DeviceBuffer() {
+        if (p) (void)hipFree(p);
+    }
+    int alloc(size_t n, const char* what = "staging") {
+        const hipError_t e = hipMalloc(&p, n ? n : 1);
+        if (e == hipSuccess) return GOL_OK;
+        p = nullptr;
+        return api_fail(GOL_ERR_OOM, std::string("hipMalloc ") + what + ": " + hipGetErrorString(e));
+    }
+    template <class T>
+    T* as() const {
+        return static_cast<T*>(p);
+    }
+};
+
+// Two timing events around work on one stream.
+struct EventPair {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    EventPair() = default;
+    EventPair(const EventPair&) = delete;
+    EventPair& operator=(const EventPair&) = delete;
+    ~EventPair() {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+    int create() {
+        GOL_HIP(hipEventCreate(&e0));
+        GOL_HIP(hipEventCreate(&e1));
+        return GOL_OK;
+    }
+    // waits for e1; microseconds from e0 to e1
+    int elapsed_us(double* us) {
+        float ms = 0;
+        GOL_HIP(hipEventSynchronize(e1));
+        GOL_HIP(hipEventElapsedTime(&ms, e0, e1));
+        *us = 1e3 * ms;
+        return GOL_OK;
+    }
+};
+
+// The pass a gol_step call takes (choose_pass); its value is the debug option "last_pass" (gol_debug.h).
+enum class Pass { None, Wave, Lanes, Coop, CoopRagged, Ring, StreamRagged, Resident, Bytes, Stream, Multi };
+
+extern const int64_t kCoopMaxCells;               // gol_policy.cpp
+constexpr int kCoopFlagWords = 1024;              // bands of one launch at most (one per CU) ...
+constexpr int kCoopErrWord = kCoopFlagWords - 1;  // ... and the error word
+
+// Per-board path and tuning options (gol_set_option; the table of names is gol_options.cpp).  The library reads no
+// environment variable: a stray one in the host process cannot change kernel paths.  Defaults are the measured ones
+// (DESIGN.md 4).
+struct BoardOptions {
+    bool coop = true;                         // "coop": cooperative register-band pass for mid-size boards
+    int coop_k = 0;                           // "coop_k": generations per hand-off (0 = min(tblock_k, 8))
+    int64_t coop_max_cells = kCoopMaxCells;   // "coop_max_cells": largest board the cooperative pass takes
+    int64_t resident_max_cells = -1;          // "resident_max_cells": LDS-resident cut-over (-1 = per layout)
+    bool wave_resident = true;                // "wave_resident": single-wave pass for boards <= 128 x 256
+    int32_t split = 0;                        // "split": streaming pair split, 1/65536 (0 = engine, < 0 = off)
+    int32_t split2 = 0;                       // "split2": three-wave groups, the middle wave's share of the two
+                                              // younger waves' rows, 1/65536 (0 = engine)
+    int64_t seg_rows = 0;                     // "seg_rows": streaming rows per wave segment (0 = planned)
+    int seam = 0;                             // "seam": torus seam strips (0 = where they apply, -1 = off)
+    bool ragged_stream = true;                // "ragged_stream": ragged boards beyond the cooperative pass stream
+                                              // packed words (0: the per-generation byte step)
+    int ragged_ring = 1;                      // "ragged_ring": ragged boards stream as block rows (torus: ring rows on
+                                              // the aligned kernel; bounded: column-masked block rows) in the aligned
+                                              // layouts: 1 from kRingMinCells cells, 2 always, 0 never (ilv-1 rows,
+                                              // bit-level row ends on a torus)
+    int coop_r = 1;                           // "coop_r": cooperative pass, rows per wave at least
+    int coop_poll_delay = -1;                 // "coop_poll_delay": s_sleep periods before a hand-off's first poll
+                                              // (-1: 0 on the cooperative pass's rows of <= 2048 cells, else 8)
+    int64_t coop_spin_limit = 0;              // "coop_spin_limit": polls before a hand-off wait gives up (0 = ~2 s)
+    int resident_threads = 1024;              // "resident_threads": LDS-resident workgroup size (1024 or 256)
+    int lanes = 2;                            // "lanes": rows-on-lanes band pass (gol_lanes.hip) in place of the
+                                              // cooperative one, for calls of >= 2 * coop depth: 2 = where it
+                                              // measured faster (use_lanes), 1 = wherever it applies, 0 = never
+    int lanes_m = 0;                          // "lanes_m": its words per lane and half-row (0 = by width, 5, 9, 17)
+    int32_t pipe_split = 0;                   // "pipe_split": level-pipelined pass (gol_pipe.hip), the oldest
+                                              // pipeline's share of a pair, 1/65536 (0 = engine, < 0 = equal shares)
+    int32_t pipe_split2 = 0;                  // "pipe_split2": its ratio after the second-oldest (0 = pipe_split)
+    bool coop_launch = false;                 // "coop_launch": persistent passes by hipLaunchCooperativeKernel (1), or
+                                              // hipLaunchKernel after the same residency check (0, the default:
+                                              // gol_internal.h launch_persistent)
+    bool view_stream = true;                  // "view_stream": wide-tile views on the streaming kernel (gol_view.hip);
+                                              // 0 = every view on the per-pixel kernel
+};
+
+}  // namespace gol
+
+struct gol_board {
+    std::mutex mu;
+    gol::BoardOptions opt;
+    bool invalid = false;  // a cooperative hand-off timed out: readbacks fail until the board is overwritten
+    bool invalid_pipe = false;  // ... or a ring wait of the level-pipelined pass (gol_pipe.hip)
+    int device = 0;
+    hipStream_t stream = nullptr;
+    int64_t W = 0, H = 0;
+    int boundary = GOL_TORUS;
+    int tblock = 16;
+    bool tblock_set = false;  // tblock_k was given at creation (a cap), not the engine default
+    bool packed = false;
+    int ilv = 0;        // words per interleaved block (packed boards), 0 = byte board
+    int64_t pitch = 0;  // words per row (packed)
+    void* buf[2] = {nullptr, nullptr};
+    int cur = 0;
+    unsigned long long* acc = nullptr;  // device scratch accumulator
+    unsigned* coop = nullptr;           // cooperative pass: per-band flags + error word (allocated on first use)
+    uint32_t* coop_xch = nullptr;       // cooperative pass: hand-off granules (allocated on first use)
+    int64_t coop_xch_words = 0;
+    unsigned coop_epoch = 0;            // tag epoch of the last cooperative launch (1..65535)
+    int64_t lanes_launches = 0;         // launches of the rows-on-lanes pass on this board (option "lanes_launches")
+    gol::Pass last_pass = gol::Pass::None;  // the pass of the last gol_step / gol_step_timed call (option "last_pass")
+    uint32_t* rag[2] = {nullptr, nullptr};  // ragged byte boards on the cooperative pass: whole-word scratch rows
+    int64_t rag_words = 0;                  // capacity of each rag buffer
+    // Ragged byte boards between gol_step calls of the multi-generation passes keep their state in the scratch rows:
+    // 0 = the bytes (cells(cur)) are current; 1 = rag[rag_cur] holds it in the streaming pass's rows (rag_pitch words),
+    // 2 = in the cooperative pass's rows, 3 = in ring rows (gol_formats.hip, layout rag_ilv).  Every other access first
+    // brings the bytes up to date (sync_bytes).
+    int rag_state = 0;
+    int rag_cur = 0;
+    int64_t rag_pitch = 0;
+    int rag_ilv = 1;
+    int ring_age = 0;  // ring rows: generations since the copies were last exact (errors reach ring_age cells in)
+    int64_t generation = 0;
+    gol::MultiBoard* multi = nullptr;  // num_gpus > 1: row strips over several devices (gol_multi.h)
+
+    size_t bytes() const { return packed ? (size_t)(pitch * H) * 4 : (size_t)(W * H); }
+    uint32_t* words(int i) { return static_cast<uint32_t*>(buf[i]); }
+    uint8_t* cells(int i) { return static_cast<uint8_t*>(buf[i]); }
+
+    gol::StreamArgs stream_args(int64_t out_begin, int64_t out_end, int k) const {
+        gol::StreamArgs a{};
+        a.words = W / 32;
+        a.pitch = pitch;
+        a.rows = H;
+        a.height = H;
+        a.out_begin = out_begin;
+        a.out_end = out_end;
+        a.ilv = ilv;
+        a.split_opt = opt.split;
+        a.split2_opt = opt.split2;
+        a.seg_opt = opt.seg_rows;
+        a.seam_opt = opt.seam;
+        a.pipe_split_opt = opt.pipe_split;
+        a.pipe_split2_opt = opt.pipe_split2;
+        a.pipe_err = coop ? reinterpret_cast<int*>(coop + gol::kCoopErrWord) : nullptr;
+        return a;
+    }
+};
+
+namespace gol {
+
+// No C++ exception past the extern "C" boundary: allocation failures are GOL_ERR_OOM.
+template <class F>
+int guarded(F&& f) {
+    try {
+        return f();
+    } catch (const std::exception& ex) {  // std::bad_alloc among them
+        return fail(GOL_ERR_OOM, ex.what());
+    } catch (...) {
+        return fail(GOL_ERR_INVALID, "unknown exception");
+    }
+}
+
+// The guarded entry of every board call that touches the device: the null check, the board's lock, its device.
+// Argument checks go inside `f`, so a null board wins over a second bad argument.
+template <class F>
+int with_board(gol_board* b, F&& f) {
+    if (!b) return fail(GOL_ERR_INVALID, "null board");
+    return guarded([&] {
+        std::lock_guard<std::mutex> g(b->mu);
+        DeviceGuard dg(b->device);
+        return f();
+    });
+}
+
+// ---- gol_capi.cpp: after a synchronisation, GOL_ERR_HIP if a pass left the board invalid; a ragged board's bytes
+// brought up to date from its scratch rows
+int check_valid(gol_board* b);
+int sync_bytes(gol_board* b);
+
+// ---- gol_policy.cpp: the layout and depth a new board gets, and the pass a gol_step call takes
+int board_tblock(int ilv, int64_t cells, int boundary);
+// packed, ilv, pitch, tblock and tblock_set of a new W x H board of `nparts` row strips; tblock_k and ilv as given to
+// gol_create_ex (0: the engine's choice)
+void board_layout(gol_board* b, int nparts, int tblock_k, int ilv);
+int coop_depth(const gol_board* b);
+int lanes_depth(const gol_board* b);
+int ring_ilv(const gol_board* b);
+struct PassChoice {
+    Pass pass;
+    int64_t rag_pitch;  // CoopRagged: words per scratch row
+};
+PassChoice choose_pass(const gol_board* b, int64_t gens);
+
+// ---- gol_strip.cpp
+int check_view(const gol_view* v, int64_t width, int64_t height, int boundary);
+
+}  // namespace gol

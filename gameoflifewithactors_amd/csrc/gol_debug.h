@@ -12,6 +12,10 @@
  *   "coop_launch" 0 | 1         persistent passes by hipLaunchKernel after a residency check (0), or by
  *                               hipLaunchCooperativeKernel (1; DESIGN.md 6 "Exit under rocprofv3")
  *   "lanes_launches"            (read-only) launches of the rows-on-lanes pass on this board
+ *   "last_pass"                 (read-only) the pass the last gol_step / gol_step_timed call took, as gol::Pass
+ *                               (gol_board.h): 0 none yet, 1 single-wave, 2 rows-on-lanes, 3 cooperative, 4 cooperative on
+ *                               a ragged board's scratch rows, 5 block (ring) rows, 6 ragged streaming, 7 LDS-resident,
+ *                               8 byte step, 9 streaming, 10 multi-part
  * Unknown names return GOL_ERR_INVALID.
  */
 #ifndef GOL_DEBUG_H

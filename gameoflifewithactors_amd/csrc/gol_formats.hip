@@ -212,7 +212,7 @@ __global__ __launch_bounds__(256) void gol_unpack_ring(const uint32_t* __restric
 // suffix spans 64 .. 127 positions).  One wavefront per row; every lane issues its (at most 4) loads before the first
 // ballot, so a row costs one memory round trip.  Every source position lies in [64, 64 + W), which this kernel never
 // writes.  The host runs it only when the errors from the extended row's two ends could reach the board's cells on
-// the next pass: they spread one cell per generation, so every 64 / k passes (gol_capi.cpp ring_age).
+// the next pass: they spread one cell per generation, so every 64 / k passes (gol_passes.cpp run_ring, ring_age).
 __global__ __launch_bounds__(256) void gol_ring_refresh(uint32_t* __restrict__ words, int64_t W, int64_t H,
                                                         int64_t pitch, int ilv) {
     const int64_t y = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -458,7 +458,7 @@ __global__ void gol_import_canonical(const uint64_t* __restrict__ in, int64_t W,
 }
 
 // ------------------------------------------------------------------------------------------------
-// Launchers (host).  Geometry was validated by the caller (gol_capi.cpp).
+// Launchers (host).  Geometry was validated by the caller (gol_capi.cpp, gol_strip.cpp).
 
 static inline unsigned grid1d(int64_t n, int block = 256) {
     int64_t g = (n + block - 1) / block;

@@ -1,4 +1,5 @@
-// gol_internal.h -- launcher prototypes shared by the kernel files and gol_capi.cpp (not installed).
+// gol_internal.h -- launcher prototypes shared by the kernel files and the host files (gol_capi.cpp, gol_passes.cpp,
+// gol_strip.cpp, gol_policy.cpp; not installed).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -155,7 +156,7 @@ struct ViewSource {
     bool torus;
 };
 struct ViewArgs {
-    int64_t x, y, s, out_w, out_h;  // validated by the caller (gol_capi.cpp check_view)
+    int64_t x, y, s, out_w, out_h;  // validated by the caller (gol_strip.cpp check_view)
 };
 // ADDS the counts of the owned rows into counts[out_w * out_h] (one launch per non-wrapping rectangle of the view:
 // up to four on a torus).  stream_kernel: wide tiles of packed boards (s >= 16 ilv; two tiles per word from 32 ilv, three

@@ -6,45 +6,16 @@
 // one-process-per-GPU path runs over torch.distributed (strips.py).  Here one process drives every part: the
 // exchange is a peer copy ordered by HIP events (the default), or on request (gol_set_option "transport") RCCL
 // send/recv over a communicator spanning the parts' devices (ncclCommInitAll) when every part has its own GPU.
-#include "gol_multi.h"
-
 #include <dlfcn.h>
 #include <rccl/rccl.h>
 
 #include <algorithm>
 
-#include "gol_internal.h"
+#include "gol_board.h"
 
 namespace gol {
 
-#define GOL_MHIP(expr)                                                                                    \
-    do {                                                                                                  \
-        hipError_t e_ = (expr);                                                                           \
-        if (e_ != hipSuccess) return api_fail(GOL_ERR_HIP, std::string(#expr ": ") + hipGetErrorString(e_)); \
-    } while (0)
-#define GOL_MRC(expr)              \
-    do {                           \
-        int rc_ = (expr);          \
-        if (rc_ != GOL_OK) return rc_; \
-    } while (0)
-
 namespace {
-
-// device staging buffer freed on every exit path
-struct Staging {
-    void* p = nullptr;
-    ~Staging() {
-        if (p) (void)hipFree(p);
-    }
-    int alloc(size_t n) {
-        hipError_t e = hipMalloc(&p, n ? n : 1);
-        if (e != hipSuccess) {
-            p = nullptr;
-            return api_fail(GOL_ERR_OOM, std::string("hipMalloc staging: ") + hipGetErrorString(e));
-        }
-        return GOL_OK;
-    }
-};
 
 // RCCL, resolved at run time (dlopen): a process that never builds a multi-GPU board does not need librccl, and a
 // process that already loaded one (torch bundles its own under the same soname) shares it instead of loading a
@@ -124,9 +95,9 @@ int MultiBoard::init_rccl() {
 int MultiBoard::set_transport(int transport) {
     if (transport != GOL_TRANSPORT_PEER && transport != GOL_TRANSPORT_RCCL)
         return api_fail(GOL_ERR_INVALID, "transport must be 1 (peer copies) or 2 (RCCL)");
-    GOL_MRC(synchronize());  // no pass of the old transport is in flight
+    GOL_RC(synchronize());  // no pass of the old transport is in flight
     if (transport == GOL_TRANSPORT_RCCL) {
-        GOL_MRC(init_rccl());
+        GOL_RC(init_rccl());
         rccl_ = true;
         transport_note_ = "RCCL ncclSend/ncclRecv over one communicator per part (ncclCommInitAll, " +
                           std::to_string(parts_.size()) + " devices)";
@@ -138,7 +109,7 @@ int MultiBoard::set_transport(int transport) {
     return GOL_OK;
 }
 
-// gol_strip_step with the board's streaming options (gol_capi.cpp)
+// gol_strip_step with the board's streaming options (gol_strip.cpp)
 int MultiBoard::strip_step(const gol_strip& s, const uint32_t* src, uint32_t* dst, int k, int64_t b, int64_t e,
                            hipStream_t st) const {
     return strip_step_opts(&s, src, dst, k, b, e, st, split_opt_, seg_opt_, seam_opt_, split2_opt_);
@@ -174,13 +145,13 @@ int MultiBoard::init(int64_t width, int64_t height, int boundary, const int* dev
         const bool torus = boundary == GOL_TORUS;
         p.up = r > 0 ? r - 1 : (torus ? n - 1 : -1);
         p.down = r < n - 1 ? r + 1 : (torus ? 0 : -1);
-        GOL_MHIP(hipSetDevice(p.device));
-        GOL_MHIP(hipStreamCreateWithFlags(&p.compute, hipStreamNonBlocking));
-        GOL_MHIP(hipStreamCreateWithFlags(&p.edge, hipStreamNonBlocking));
-        GOL_MHIP(hipStreamCreateWithFlags(&p.copy, hipStreamNonBlocking));
-        GOL_MHIP(hipEventCreateWithFlags(&p.ev_start, hipEventDisableTiming));
-        GOL_MHIP(hipEventCreateWithFlags(&p.ev_copied, hipEventDisableTiming));
-        GOL_MHIP(hipEventCreateWithFlags(&p.ev_edge, hipEventDisableTiming));
+        GOL_HIP(hipSetDevice(p.device));
+        GOL_HIP(hipStreamCreateWithFlags(&p.compute, hipStreamNonBlocking));
+        GOL_HIP(hipStreamCreateWithFlags(&p.edge, hipStreamNonBlocking));
+        GOL_HIP(hipStreamCreateWithFlags(&p.copy, hipStreamNonBlocking));
+        GOL_HIP(hipEventCreateWithFlags(&p.ev_start, hipEventDisableTiming));
+        GOL_HIP(hipEventCreateWithFlags(&p.ev_copied, hipEventDisableTiming));
+        GOL_HIP(hipEventCreateWithFlags(&p.ev_edge, hipEventDisableTiming));
         const size_t bytes = (size_t)((p.s.rows + 2 * p.s.ghost) * p.s.pitch) * 4;
         for (auto& b : p.buf) {
             hipError_t e = hipMalloc(&b, bytes);
@@ -188,9 +159,9 @@ int MultiBoard::init(int64_t width, int64_t height, int boundary, const int* dev
                 b = nullptr;
                 return api_fail(GOL_ERR_OOM, std::string("hipMalloc strip: ") + hipGetErrorString(e));
             }
-            GOL_MHIP(hipMemsetAsync(b, 0, bytes, p.compute));
+            GOL_HIP(hipMemsetAsync(b, 0, bytes, p.compute));
         }
-        GOL_MHIP(hipMalloc(&p.acc, 64));
+        GOL_HIP(hipMalloc(&p.acc, 64));
     }
     // peer copies by default; RCCL on request (set_transport) when every part has its own device
     std::vector<int> seen;
@@ -208,7 +179,7 @@ int MultiBoard::init(int64_t width, int64_t height, int boundary, const int* dev
             if (q < 0 || parts_[(size_t)q].device == p.device) continue;
             int can = 0;
             if (hipDeviceCanAccessPeer(&can, p.device, parts_[(size_t)q].device) == hipSuccess && can) {
-                GOL_MHIP(hipSetDevice(p.device));
+                GOL_HIP(hipSetDevice(p.device));
                 hipError_t e = hipDeviceEnablePeerAccess(parts_[(size_t)q].device, 0);
                 if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled)
                     return api_fail(GOL_ERR_HIP, std::string("hipDeviceEnablePeerAccess: ") + hipGetErrorString(e));
@@ -236,37 +207,37 @@ MultiBoard::~MultiBoard() {
 
 int MultiBoard::synchronize() {
     for (const Part& p : parts_) {
-        GOL_MHIP(hipSetDevice(p.device));
-        GOL_MHIP(hipStreamSynchronize(p.copy));
-        GOL_MHIP(hipStreamSynchronize(p.edge));
-        GOL_MHIP(hipStreamSynchronize(p.compute));
+        GOL_HIP(hipSetDevice(p.device));
+        GOL_HIP(hipStreamSynchronize(p.copy));
+        GOL_HIP(hipStreamSynchronize(p.edge));
+        GOL_HIP(hipStreamSynchronize(p.compute));
     }
     return GOL_OK;
 }
 
 int MultiBoard::set_cells(const uint8_t* host) {
     for (Part& p : parts_) {
-        GOL_MHIP(hipSetDevice(p.device));
+        GOL_HIP(hipSetDevice(p.device));
         const size_t n = (size_t)(p.s.rows * W_);
-        Staging st;
-        GOL_MRC(st.alloc(n));
-        GOL_MHIP(hipMemcpyAsync(st.p, host + p.s.y0 * W_, n, hipMemcpyHostToDevice, p.compute));
-        GOL_MRC(gol_strip_pack(&p.s, static_cast<const uint8_t*>(st.p), p.buf[cur_], p.compute));
-        GOL_MHIP(hipStreamSynchronize(p.compute));
+        DeviceBuffer st;
+        GOL_RC(st.alloc(n));
+        GOL_HIP(hipMemcpyAsync(st.p, host + p.s.y0 * W_, n, hipMemcpyHostToDevice, p.compute));
+        GOL_RC(gol_strip_pack(&p.s, static_cast<const uint8_t*>(st.p), p.buf[cur_], p.compute));
+        GOL_HIP(hipStreamSynchronize(p.compute));
     }
     return GOL_OK;
 }
 
 int MultiBoard::readback(uint8_t* host, int64_t stride, uint8_t value) {
     for (Part& p : parts_) {
-        GOL_MHIP(hipSetDevice(p.device));
+        GOL_HIP(hipSetDevice(p.device));
         const size_t n = (size_t)(p.s.rows * stride);
-        Staging st;
-        GOL_MRC(st.alloc(n));
-        if (stride != W_) GOL_MHIP(hipMemsetAsync(st.p, 0, n, p.compute));
-        GOL_MRC(gol_strip_unpack(&p.s, p.buf[cur_], static_cast<uint8_t*>(st.p), stride, value, p.compute));
-        GOL_MHIP(hipMemcpyAsync(host + p.s.y0 * stride, st.p, n, hipMemcpyDeviceToHost, p.compute));
-        GOL_MHIP(hipStreamSynchronize(p.compute));
+        DeviceBuffer st;
+        GOL_RC(st.alloc(n));
+        if (stride != W_) GOL_HIP(hipMemsetAsync(st.p, 0, n, p.compute));
+        GOL_RC(gol_strip_unpack(&p.s, p.buf[cur_], static_cast<uint8_t*>(st.p), stride, value, p.compute));
+        GOL_HIP(hipMemcpyAsync(host + p.s.y0 * stride, st.p, n, hipMemcpyDeviceToHost, p.compute));
+        GOL_HIP(hipStreamSynchronize(p.compute));
     }
     return GOL_OK;
 }
@@ -275,14 +246,14 @@ int MultiBoard::region(int64_t x, int64_t y, int64_t w, int64_t h, uint8_t* out)
     for (Part& p : parts_) {
         const int64_t r0 = std::max(y, p.s.y0), r1 = std::min(y + h, p.s.y0 + p.s.rows);
         if (r0 >= r1) continue;
-        GOL_MHIP(hipSetDevice(p.device));
+        GOL_HIP(hipSetDevice(p.device));
         const size_t n = (size_t)((r1 - r0) * w);
-        Staging st;
-        GOL_MRC(st.alloc(n));
-        GOL_MHIP(launch_region(p.buf[cur_] + p.s.ghost * p.s.pitch, ilv_, W_, p.s.pitch, x, r0 - p.s.y0, w, r1 - r0,
+        DeviceBuffer st;
+        GOL_RC(st.alloc(n));
+        GOL_HIP(launch_region(p.buf[cur_] + p.s.ghost * p.s.pitch, ilv_, W_, p.s.pitch, x, r0 - p.s.y0, w, r1 - r0,
                                static_cast<uint8_t*>(st.p), p.compute));
-        GOL_MHIP(hipMemcpyAsync(out + (r0 - y) * w, st.p, n, hipMemcpyDeviceToHost, p.compute));
-        GOL_MHIP(hipStreamSynchronize(p.compute));
+        GOL_HIP(hipMemcpyAsync(out + (r0 - y) * w, st.p, n, hipMemcpyDeviceToHost, p.compute));
+        GOL_HIP(hipStreamSynchronize(p.compute));
     }
     return GOL_OK;
 }
@@ -290,14 +261,14 @@ int MultiBoard::region(int64_t x, int64_t y, int64_t w, int64_t h, uint8_t* out)
 int MultiBoard::save_packed(uint64_t* host) {
     const int64_t nc = (W_ + 63) / 64;
     for (Part& p : parts_) {
-        GOL_MHIP(hipSetDevice(p.device));
+        GOL_HIP(hipSetDevice(p.device));
         const size_t n = (size_t)(p.s.rows * nc) * 8;
-        Staging st;
-        GOL_MRC(st.alloc(n));
-        GOL_MHIP(launch_export_canonical(p.buf[cur_], W_, p.s.rows, p.s.pitch, p.s.ghost, ilv_,
+        DeviceBuffer st;
+        GOL_RC(st.alloc(n));
+        GOL_HIP(launch_export_canonical(p.buf[cur_], W_, p.s.rows, p.s.pitch, p.s.ghost, ilv_,
                                          static_cast<uint64_t*>(st.p), p.compute));
-        GOL_MHIP(hipMemcpyAsync(host + p.s.y0 * nc, st.p, n, hipMemcpyDeviceToHost, p.compute));
-        GOL_MHIP(hipStreamSynchronize(p.compute));
+        GOL_HIP(hipMemcpyAsync(host + p.s.y0 * nc, st.p, n, hipMemcpyDeviceToHost, p.compute));
+        GOL_HIP(hipStreamSynchronize(p.compute));
     }
     return GOL_OK;
 }
@@ -305,31 +276,31 @@ int MultiBoard::save_packed(uint64_t* host) {
 int MultiBoard::load_packed(const uint64_t* host) {
     const int64_t nc = (W_ + 63) / 64;
     for (Part& p : parts_) {
-        GOL_MHIP(hipSetDevice(p.device));
+        GOL_HIP(hipSetDevice(p.device));
         const size_t n = (size_t)(p.s.rows * nc) * 8;
-        Staging st;
-        GOL_MRC(st.alloc(n));
-        GOL_MHIP(hipMemcpyAsync(st.p, host + p.s.y0 * nc, n, hipMemcpyHostToDevice, p.compute));
-        GOL_MHIP(launch_import_canonical(static_cast<const uint64_t*>(st.p), W_, p.s.rows, p.s.pitch, p.s.ghost, ilv_,
+        DeviceBuffer st;
+        GOL_RC(st.alloc(n));
+        GOL_HIP(hipMemcpyAsync(st.p, host + p.s.y0 * nc, n, hipMemcpyHostToDevice, p.compute));
+        GOL_HIP(launch_import_canonical(static_cast<const uint64_t*>(st.p), W_, p.s.rows, p.s.pitch, p.s.ghost, ilv_,
                                          p.buf[cur_], p.compute));
-        GOL_MHIP(hipStreamSynchronize(p.compute));
+        GOL_HIP(hipStreamSynchronize(p.compute));
     }
     return GOL_OK;
 }
 
 int MultiBoard::seed_splitmix(uint64_t seed) {
     for (Part& p : parts_) {
-        GOL_MHIP(hipSetDevice(p.device));
-        GOL_MRC(gol_strip_seed_splitmix(&p.s, p.buf[cur_], seed, p.compute));
+        GOL_HIP(hipSetDevice(p.device));
+        GOL_RC(gol_strip_seed_splitmix(&p.s, p.buf[cur_], seed, p.compute));
     }
     return synchronize();
 }
 
 int MultiBoard::clear() {
     for (Part& p : parts_) {
-        GOL_MHIP(hipSetDevice(p.device));
+        GOL_HIP(hipSetDevice(p.device));
         const size_t bytes = (size_t)((p.s.rows + 2 * p.s.ghost) * p.s.pitch) * 4;
-        GOL_MHIP(hipMemsetAsync(p.buf[cur_], 0, bytes, p.compute));
+        GOL_HIP(hipMemsetAsync(p.buf[cur_], 0, bytes, p.compute));
     }
     return synchronize();
 }
@@ -343,13 +314,13 @@ int MultiBoard::place_points(const std::vector<int64_t>& xy) {
                 mine.push_back(xy[i + 1] - p.s.y0);  // owned row
             }
         if (mine.empty()) continue;
-        GOL_MHIP(hipSetDevice(p.device));
-        Staging st;
-        GOL_MRC(st.alloc(mine.size() * sizeof(int64_t)));
-        GOL_MHIP(hipMemcpyAsync(st.p, mine.data(), mine.size() * sizeof(int64_t), hipMemcpyHostToDevice, p.compute));
-        GOL_MHIP(launch_set_points(p.buf[cur_] + p.s.ghost * p.s.pitch, ilv_, W_, p.s.pitch,
+        GOL_HIP(hipSetDevice(p.device));
+        DeviceBuffer st;
+        GOL_RC(st.alloc(mine.size() * sizeof(int64_t)));
+        GOL_HIP(hipMemcpyAsync(st.p, mine.data(), mine.size() * sizeof(int64_t), hipMemcpyHostToDevice, p.compute));
+        GOL_HIP(launch_set_points(p.buf[cur_] + p.s.ghost * p.s.pitch, ilv_, W_, p.s.pitch,
                                    static_cast<const int64_t*>(st.p), (int64_t)mine.size() / 2, p.compute));
-        GOL_MHIP(hipStreamSynchronize(p.compute));
+        GOL_HIP(hipStreamSynchronize(p.compute));
     }
     return GOL_OK;
 }
@@ -357,14 +328,14 @@ int MultiBoard::place_points(const std::vector<int64_t>& xy) {
 int MultiBoard::reduce(bool hash, uint64_t* out) {
     uint64_t sum = 0;
     for (Part& p : parts_) {
-        GOL_MHIP(hipSetDevice(p.device));
-        GOL_MHIP(hipMemsetAsync(p.acc, 0, sizeof(unsigned long long), p.compute));
+        GOL_HIP(hipSetDevice(p.device));
+        GOL_HIP(hipMemsetAsync(p.acc, 0, sizeof(unsigned long long), p.compute));
         uint64_t* acc = reinterpret_cast<uint64_t*>(p.acc);
-        GOL_MRC(hash ? gol_strip_hash_partial(&p.s, p.buf[cur_], acc, p.compute)
+        GOL_RC(hash ? gol_strip_hash_partial(&p.s, p.buf[cur_], acc, p.compute)
                      : gol_strip_population(&p.s, p.buf[cur_], acc, p.compute));
         unsigned long long v = 0;
-        GOL_MHIP(hipMemcpyAsync(&v, p.acc, sizeof(v), hipMemcpyDeviceToHost, p.compute));
-        GOL_MHIP(hipStreamSynchronize(p.compute));
+        GOL_HIP(hipMemcpyAsync(&v, p.acc, sizeof(v), hipMemcpyDeviceToHost, p.compute));
+        GOL_HIP(hipStreamSynchronize(p.compute));
         sum += (uint64_t)v;  // hash partials add with wrap-around
     }
     *out = hash ? gol_hash_finalize(sum, W_, H_) : sum;
@@ -376,21 +347,21 @@ int MultiBoard::view_counts(const gol_view* v, uint32_t* counts, bool stream_ker
     std::fill(counts, counts + n, 0u);
     // the parts whose owned rows the view can meet launch first, each on its own device and stream ...
     std::vector<std::vector<uint32_t>> host(parts_.size());
-    std::vector<Staging> dev(parts_.size());  // freed (hipFree drains the device) before the host buffers go
+    std::vector<DeviceBuffer> dev(parts_.size());  // freed (hipFree drains the device) before the host buffers go
     for (size_t i = 0; i < parts_.size(); i++) {
         Part& p = parts_[i];
-        GOL_MHIP(hipSetDevice(p.device));
-        GOL_MRC(dev[i].alloc(n * sizeof(uint32_t)));
+        GOL_HIP(hipSetDevice(p.device));
+        GOL_RC(dev[i].alloc(n * sizeof(uint32_t)));
         host[i].resize(n);
-        GOL_MHIP(hipMemsetAsync(dev[i].p, 0, n * sizeof(uint32_t), p.compute));
-        GOL_MRC(strip_view_counts_opts(&p.s, p.buf[cur_], v, static_cast<uint32_t*>(dev[i].p), p.compute,
+        GOL_HIP(hipMemsetAsync(dev[i].p, 0, n * sizeof(uint32_t), p.compute));
+        GOL_RC(strip_view_counts_opts(&p.s, p.buf[cur_], v, static_cast<uint32_t*>(dev[i].p), p.compute,
                                        stream_kernel));
-        GOL_MHIP(hipMemcpyAsync(host[i].data(), dev[i].p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, p.compute));
+        GOL_HIP(hipMemcpyAsync(host[i].data(), dev[i].p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, p.compute));
     }
     // ... then the host adds the partials (tiles that straddle two strips get a share from each)
     for (size_t i = 0; i < parts_.size(); i++) {
-        GOL_MHIP(hipSetDevice(parts_[i].device));
-        GOL_MHIP(hipStreamSynchronize(parts_[i].compute));
+        GOL_HIP(hipSetDevice(parts_[i].device));
+        GOL_HIP(hipStreamSynchronize(parts_[i].compute));
         for (size_t k = 0; k < n; k++) counts[k] += host[i][k];
     }
     return GOL_OK;
@@ -410,21 +381,21 @@ int MultiBoard::view_counts(const gol_view* v, uint32_t* counts, bool stream_ker
 int MultiBoard::exchange_peer(int k) {
     const size_t row_bytes = (size_t)W_ / 8;  // pitch == width / 32 words
     for (Part& p : parts_) {
-        GOL_MHIP(hipSetDevice(p.device));
-        GOL_MHIP(hipStreamWaitEvent(p.copy, p.ev_start, 0));
+        GOL_HIP(hipSetDevice(p.device));
+        GOL_HIP(hipStreamWaitEvent(p.copy, p.ev_start, 0));
         const uint32_t* src = p.buf[cur_];
         if (p.up >= 0) {
             Part& u = parts_[(size_t)p.up];
-            GOL_MHIP(hipMemcpyPeerAsync(u.buf[cur_] + (u.s.ghost + u.s.rows) * u.s.pitch, u.device,
+            GOL_HIP(hipMemcpyPeerAsync(u.buf[cur_] + (u.s.ghost + u.s.rows) * u.s.pitch, u.device,
                                         src + p.s.ghost * p.s.pitch, p.device, k * row_bytes, p.copy));
         }
         if (p.down >= 0) {
             Part& d = parts_[(size_t)p.down];
-            GOL_MHIP(hipMemcpyPeerAsync(d.buf[cur_] + (d.s.ghost - k) * d.s.pitch, d.device,
+            GOL_HIP(hipMemcpyPeerAsync(d.buf[cur_] + (d.s.ghost - k) * d.s.pitch, d.device,
                                         src + (p.s.ghost + p.s.rows - k) * p.s.pitch, p.device, k * row_bytes,
                                         p.copy));
         }
-        GOL_MHIP(hipEventRecord(p.ev_copied, p.copy));
+        GOL_HIP(hipEventRecord(p.ev_copied, p.copy));
     }
     return GOL_OK;
 }
@@ -436,8 +407,8 @@ int MultiBoard::exchange_rccl(int k) {
     const Rccl& nc = Rccl::get();
     const std::vector<gol_xfer> plan = exchange_plan(H_, boundary_, (int)parts_.size(), max_k_, k);
     for (Part& p : parts_) {
-        GOL_MHIP(hipSetDevice(p.device));
-        GOL_MHIP(hipStreamWaitEvent(p.copy, p.ev_start, 0));
+        GOL_HIP(hipSetDevice(p.device));
+        GOL_HIP(hipStreamWaitEvent(p.copy, p.ev_start, 0));
     }
     ncclResult_t r = nc.group_start();
     if (r != ncclSuccess) return api_fail(GOL_ERR_HIP, "ncclGroupStart: " + nc.why(r));
@@ -455,8 +426,8 @@ int MultiBoard::exchange_rccl(int k) {
     r = nc.group_end();
     if (r != ncclSuccess) return api_fail(GOL_ERR_HIP, "ncclGroupEnd: " + nc.why(r));
     for (Part& p : parts_) {
-        GOL_MHIP(hipSetDevice(p.device));
-        GOL_MHIP(hipEventRecord(p.ev_copied, p.copy));
+        GOL_HIP(hipSetDevice(p.device));
+        GOL_HIP(hipEventRecord(p.ev_copied, p.copy));
     }
     return GOL_OK;
 }
@@ -464,14 +435,14 @@ int MultiBoard::exchange_rccl(int k) {
 int MultiBoard::pass(int k, std::vector<PassTimer>* timers) {
     for (size_t i = 0; i < parts_.size(); i++) {
         Part& p = parts_[i];
-        GOL_MHIP(hipSetDevice(p.device));
-        if (timers) GOL_MHIP(hipEventRecord((*timers)[i].t0, p.compute));
-        GOL_MHIP(hipEventRecord(p.ev_start, p.compute));
+        GOL_HIP(hipSetDevice(p.device));
+        if (timers) GOL_HIP(hipEventRecord((*timers)[i].t0, p.compute));
+        GOL_HIP(hipEventRecord(p.ev_start, p.compute));
     }
-    GOL_MRC(rccl_ ? exchange_rccl(k) : exchange_peer(k));
+    GOL_RC(rccl_ ? exchange_rccl(k) : exchange_peer(k));
     for (size_t i = 0; i < parts_.size(); i++) {
         Part& p = parts_[i];
-        GOL_MHIP(hipSetDevice(p.device));
+        GOL_HIP(hipSetDevice(p.device));
         const uint32_t* src = p.buf[cur_];
         uint32_t* dst = p.buf[cur_ ^ 1];
         const int64_t rows = p.s.rows;
@@ -479,26 +450,26 @@ int MultiBoard::pass(int k, std::vector<PassTimer>* timers) {
         if (lo < hi) {
             // leave room on the device for the two edge bands, which start as soon as the ghost rows land
             int64_t w0 = 0, w1 = 0;
-            GOL_MRC(strip_plan_opts(&p.s, k, 0, lo, &w0, nullptr, split_opt_, seg_opt_, seam_opt_, split2_opt_));
-            GOL_MRC(strip_plan_opts(&p.s, k, hi, rows, &w1, nullptr, split_opt_, seg_opt_, seam_opt_, split2_opt_));
+            GOL_RC(strip_plan_opts(&p.s, k, 0, lo, &w0, nullptr, split_opt_, seg_opt_, seam_opt_, split2_opt_));
+            GOL_RC(strip_plan_opts(&p.s, k, hi, rows, &w1, nullptr, split_opt_, seg_opt_, seam_opt_, split2_opt_));
             gol_strip s = p.s;
             s.spare_waves = (int32_t)std::min<int64_t>(w0 + w1, 1 << 20);
-            GOL_MRC(strip_step(s, src, dst, k, lo, hi, p.compute));
+            GOL_RC(strip_step(s, src, dst, k, lo, hi, p.compute));
         }
-        if (timers) GOL_MHIP(hipEventRecord((*timers)[i].interior, p.compute));
-        GOL_MHIP(hipStreamWaitEvent(p.edge, p.ev_start, 0));
+        if (timers) GOL_HIP(hipEventRecord((*timers)[i].interior, p.compute));
+        GOL_HIP(hipStreamWaitEvent(p.edge, p.ev_start, 0));
         if (rccl_) {
-            GOL_MHIP(hipStreamWaitEvent(p.edge, p.ev_copied, 0));  // my receives landed
+            GOL_HIP(hipStreamWaitEvent(p.edge, p.ev_copied, 0));  // my receives landed
         } else {
             for (int q : {p.up, p.down})
-                if (q >= 0) GOL_MHIP(hipStreamWaitEvent(p.edge, parts_[(size_t)q].ev_copied, 0));
+                if (q >= 0) GOL_HIP(hipStreamWaitEvent(p.edge, parts_[(size_t)q].ev_copied, 0));
         }
-        if (timers) GOL_MHIP(hipEventRecord((*timers)[i].go, p.edge));
-        GOL_MRC(strip_step(p.s, src, dst, k, 0, lo, p.edge));
-        GOL_MRC(strip_step(p.s, src, dst, k, hi, rows, p.edge));
-        if (timers) GOL_MHIP(hipEventRecord((*timers)[i].edge, p.edge));
-        GOL_MHIP(hipEventRecord(p.ev_edge, p.edge));
-        GOL_MHIP(hipStreamWaitEvent(p.compute, p.ev_edge, 0));
+        if (timers) GOL_HIP(hipEventRecord((*timers)[i].go, p.edge));
+        GOL_RC(strip_step(p.s, src, dst, k, 0, lo, p.edge));
+        GOL_RC(strip_step(p.s, src, dst, k, hi, rows, p.edge));
+        if (timers) GOL_HIP(hipEventRecord((*timers)[i].edge, p.edge));
+        GOL_HIP(hipEventRecord(p.ev_edge, p.edge));
+        GOL_HIP(hipStreamWaitEvent(p.compute, p.ev_edge, 0));
     }
     cur_ ^= 1;
     return GOL_OK;
@@ -572,7 +543,7 @@ int MultiBoard::step_timed(int64_t generations, int64_t* done, double* elapsed_u
 int MultiBoard::step(int64_t generations, int64_t* done) {
     while (generations > 0) {
         const int k = stream_largest_k(generations, max_k_, ilv_, W_ / 32, boundary_ == GOL_BOUNDED);
-        GOL_MRC(pass(k));
+        GOL_RC(pass(k));
         generations -= k;
         *done += k;
     }

@@ -26,15 +26,14 @@
 
 namespace gol {
 
-int api_fail(int code, const std::string& msg);  // sets gol_last_error (gol_capi.cpp)
 // gol_strip_step / gol_strip_plan with a board's streaming options ("split", "seg_rows", "seam", "split2";
-// gol_capi.cpp)
+// gol_strip.cpp)
 int strip_step_opts(const gol_strip* s, const uint32_t* src, uint32_t* dst, int k, int64_t out_begin, int64_t out_end,
                     hipStream_t stream, int32_t split_opt, int64_t seg_opt, int32_t seam_opt, int32_t split2_opt = 0);
 int strip_plan_opts(const gol_strip* s, int k, int64_t out_begin, int64_t out_end, int64_t* waves, int64_t* seg_rows,
                     int32_t split_opt, int64_t seg_opt, int32_t seam_opt, int32_t split2_opt = 0);
 
-// gol_strip_view_counts with a board's "view_stream" option (gol_capi.cpp)
+// gol_strip_view_counts with a board's "view_stream" option (gol_strip.cpp)
 int strip_view_counts_opts(const gol_strip* s, const uint32_t* buf, const gol_view* v, uint32_t* dev_counts,
                            hipStream_t stream, bool stream_kernel);
 

@@ -23,6 +23,46 @@ def test_bitlogic_exhaustive_on_host(tmp_path):
     assert '"mismatches": 0' in out
 
 
+# the strings tests/cpp/test_seed_rle.cpp parses, under the names it prints them with
+RLE = {
+    "glider": "bo$2bo$3o!",
+    "header": "#N Gosper glider gun\n#C a comment\nx = 36, y = 9, rule = B3/S23\n24bo$22bobo$12b2o6b2o12b2o$11bo3bo4b2o12b2o$\n"
+              "2o8bo5bo3b2o$2o8bo3bob2o4bobo$10bo5bo7bo$11bo3bo$12b2o!",
+    "long_runs": "12o13$\n15b10o2$ 3o.A!",
+}
+
+
+def test_seed_and_rle_on_host(tmp_path, oracle):
+    """csrc/gol_seed_rle.h, the host-only header behind gol_seed_dotnet and gol_place_rle, compiled alone under the
+    address and undefined-behaviour sanitizers (tests/cpp/test_seed_rle.cpp): the first 64 values of System.Random's
+    Next() and Next(2) (GameOfLifeDriver.fs:10-11, Script.fsx:25,27) for five seeds, INT32_MIN among them, and the
+    points of a handful of RLE strings, against the oracle's own restatements; malformed RLE is an error."""
+    import json
+
+    exe = tmp_path / "test_seed_rle"
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover=all", os.path.join(HERE, "cpp", "test_seed_rle.cpp"), "-o", str(exe)],
+                   check=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    rows = [json.loads(line) for line in r.stdout.splitlines()]
+    seeds = [row for row in rows if "seed" in row]
+    assert [row["seed"] for row in seeds] == [0, 1, 42, -5, -2**31]
+    for row in seeds:
+        a, b = oracle.DotNetRandom(row["seed"]), oracle.DotNetRandom(row["seed"])
+        assert row["next"] == [a.next() for _ in range(64)], row["seed"]
+        assert row["next2"] == [b.next(2) for _ in range(64)], row["seed"]
+    rles = {row["rle"]: row for row in rows if "rle" in row}
+    assert set(rles) == set(RLE) | {"bad_character", "huge_run", "null"}
+    for name, text in RLE.items():
+        assert rles[name]["ok"], rles[name]
+        assert [tuple(p) for p in rles[name]["points"]] == oracle.parse_rle(text), name
+    assert len(rles["glider"]["points"]) == 5 and len(rles["header"]["points"]) == 36
+    for name, why in (("bad_character", "bad RLE character '?'"), ("huge_run", "RLE run length too large"),
+                      ("null", "null RLE")):
+        assert not rles[name]["ok"] and rles[name]["error"] == why and rles[name]["points"] == [], rles[name]
+
+
 def _declared_functions():
     src = open(HEADER).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
@@ -45,9 +85,9 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_debug_option_list_matches_the_library():
-    """the test knobs are listed once in the library (csrc/gol_capi.cpp kDebugOptions, exported by
-    gol_debug_option_names); the Python routing set _lib.DEBUG_OPTIONS must be exactly that list, or a knob would be
-    sent to gol_set_option (GOL_ERR_INVALID) without any test noticing."""
+    """the test knobs are listed once in the library (the rows of csrc/gol_options.cpp kOptions flagged
+    debug, exported by gol_debug_option_names); the Python routing set _lib.DEBUG_OPTIONS must be exactly that list, or
+    a knob would be sent to gol_set_option (GOL_ERR_INVALID) without any test noticing."""
     from gameoflifewithactors_amd import _lib
 
     names = _lib.load().gol_debug_option_names().decode().split(",")

@@ -138,7 +138,7 @@ def test_num_gpus_beyond_visible_devices_is_rejected(gol):
 
 
 def test_calls_restore_the_callers_device(gol, oracle):
-    """Every C-ABI call switches to the board's device and back (gol_capi.cpp DeviceGuard): a caller whose
+    """Every C-ABI call switches to the board's device and back (gol_board.h with_board, DeviceGuard): a caller whose
     current device is 1 keeps device 1 across create / step / readback / destroy of boards on device 0."""
     import torch
 

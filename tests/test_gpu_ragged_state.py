@@ -1,5 +1,5 @@
 """GPU parity of a ragged byte board whose state stays in whole-word scratch rows between gol_step calls
-(csrc/gol_capi.cpp rag_state; DESIGN.md 4.1 "Ragged rows").
+(csrc/gol_board.h rag_state, csrc/gol_passes.cpp step_impl; DESIGN.md 4.1 "Ragged rows").
 
 The streaming and cooperative passes on ragged boards (width not a multiple of 32: the reference's `size` is any
 integer, GameOfLifeLogic.fs:5) pack the byte board into scratch words once and leave the state there after the call;
