@@ -60,6 +60,41 @@ extern int gol_transport(nativeint board, int& transport, System.Text.StringBuil
 extern int gol_step_timed(nativeint board, int64 generations, double& elapsedUs)
 [<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
 extern int gol_device_count(int& n)
+// ---- batches of small boards (gol.h gol_batch_*): one wavefront per board, every board stepped by one launch
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int gol_batch_supported(int64 width, int64 height)   // host-only: rows per lane (1..4), 0 = not a batch geometry
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int gol_batch_create(int64 width, int64 height, int boundary, int64 count, nativeint& batch)
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int gol_batch_destroy(nativeint batch)
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int gol_batch_info(nativeint batch, int64& width, int64& height, int& boundary, int64& count)
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int gol_batch_set_cells(nativeint batch, int64 first, int64 n, byte[] cells, int64 len)
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int gol_batch_get_cells(nativeint batch, int64 first, int64 n, byte[] cells, int64 len)
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int gol_batch_seed_dotnet(nativeint batch, int[] seeds, int64 n, int mode)
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int gol_batch_seed_splitmix(nativeint batch, uint64 seed)
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int gol_batch_clear(nativeint batch)
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int gol_batch_step(nativeint batch, int64 generations)
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int gol_batch_step_timed(nativeint batch, int64 generations, double& elapsedUs)
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int gol_batch_step_trace(nativeint batch, int64 generations, int64 every, uint32[] trace, int64 len)
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int gol_batch_generation(nativeint batch, int64& generation)
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int gol_batch_populations(nativeint batch, int64[] populations, int64 n)
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int gol_batch_hashes(nativeint batch, uint64[] hashes, int64 n)
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int gol_batch_render_gray8(nativeint batch, int64 board, byte[] pixels, int64 stride, byte aliveValue)
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int gol_batch_synchronize(nativeint batch)
 [<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
 extern nativeint gol_last_error()
 
@@ -111,6 +146,34 @@ type Board(width: int, height: int, boundary: Boundary, ?numGpus: int) =
         check "gol_transport" (gol_transport(h, &t, note, int64 note.Capacity)); (t, note.ToString())
     interface IDisposable with
         member _.Dispose() = if h <> 0n then (gol_destroy h |> ignore; h <- 0n)
+
+/// `count` boards of the reference's size (any width 3..128 with gol_batch_supported > 0) stepped together: the ensemble
+/// the reference samples one clock seed at a time (GameOfLifeDriver.fs:9-11).  Board i is seeded like Board.Seed(seeds.[i]).
+type Batch(width: int, height: int, count: int, boundary: Boundary) =
+    let mutable h = 0n
+    do check "gol_batch_create" (gol_batch_create(int64 width, int64 height, int boundary, int64 count, &h))
+    member _.Count = count
+    member _.Seed(seeds: int[], mode: InitMode) =
+        check "gol_batch_seed_dotnet" (gol_batch_seed_dotnet(h, seeds, int64 seeds.Length, int mode))
+    member _.Step(generations: int64) = check "gol_batch_step" (gol_batch_step(h, generations))
+    /// Steps and returns trace.[t * count + i] = population of board i after generation every * (t + 1) of this call.
+    member _.StepTrace(generations: int64, every: int64) =
+        let t = Array.zeroCreate<uint32> (int (generations / every) * count)
+        check "gol_batch_step_trace" (gol_batch_step_trace(h, generations, every, t, int64 t.Length)); t
+    member _.Populations() =
+        let p = Array.zeroCreate<int64> count
+        check "gol_batch_populations" (gol_batch_populations(h, p, int64 count)); p
+    member _.Hashes() =
+        let p = Array.zeroCreate<uint64> count
+        check "gol_batch_hashes" (gol_batch_hashes(h, p, int64 count)); p
+    /// One board's Gray8 frame for the render agent (GameOfLifeUI.fs:24-28).
+    member _.Render(board: int, pixels: byte[], alive: byte) =
+        check "gol_batch_render_gray8" (gol_batch_render_gray8(h, int64 board, pixels, int64 width, alive))
+    member _.GetCells(first: int, n: int) =
+        let a = Array.zeroCreate<byte> (n * width * height)
+        check "gol_batch_get_cells" (gol_batch_get_cells(h, int64 first, int64 n, a, int64 a.Length)); a
+    interface IDisposable with
+        member _.Dispose() = if h <> 0n then (gol_batch_destroy h |> ignore; h <- 0n)
 
 /// A new Gray8 frame (outW * outH bytes) of the view: what the render agent writes to its bitmap per tick.
 let renderView (board: Board) (x: int64, y: int64, scale: int64, outW: int, outH: int) (mode: ViewMode) (alive: byte) =

@@ -5,6 +5,7 @@ applying B3/S23 every generation) with HIP kernels behind a C ABI (``include/gol
 ``libgol_hip.so``).  Python pieces:
 
 * ``board.Board``     -- one board in HBM; the C ABI's board handle
+* ``batch.BoardBatch`` -- many small boards of one size, one wavefront each, stepped by one launch
 * ``logic``           -- Grid / Location / UpdateView / apply_grid (GameOfLifeLogic.fs)
 * ``driver``          -- run() / update_view() / UpdateAgent (GameOfLifeDriver.fs, GameOfLifeUI.fs)
 * ``strips``          -- multi-GPU row strips with the halo exchange (one process per GPU)
@@ -20,4 +21,8 @@ def __getattr__(name):  # lazy: importing the package must not require the share
         from . import board
 
         return getattr(board, name)
+    if name in ("BoardBatch", "batch_supported"):
+        from . import batch
+
+        return getattr(batch, name)
     raise AttributeError(name)

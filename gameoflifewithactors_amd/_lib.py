@@ -155,7 +155,26 @@ SIGNATURES = {
     "gol_get_option": (ctypes.c_int, [vp, ctypes.c_char_p, i64p]),
     "gol_device_count": (ctypes.c_int, [ip]),
     "gol_step_timed": (ctypes.c_int, [vp, i64, ctypes.POINTER(ctypes.c_double)]),
+    # the batch handle (gol_batch*: many small boards, one wavefront each)
+    "gol_batch_supported": (ctypes.c_int, [i64, i64]),
+    "gol_batch_create": (ctypes.c_int, [i64, i64, ctypes.c_int, i64, ctypes.POINTER(vp)]),
+    "gol_batch_destroy": (ctypes.c_int, [vp]),
+    "gol_batch_info": (ctypes.c_int, [vp, i64p, i64p, ip, i64p]),
+    "gol_batch_set_cells": (ctypes.c_int, [vp, i64, i64, u8p, i64]),
+    "gol_batch_get_cells": (ctypes.c_int, [vp, i64, i64, u8p, i64]),
+    "gol_batch_seed_dotnet": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int32), i64, ctypes.c_int]),
+    "gol_batch_seed_splitmix": (ctypes.c_int, [vp, u64]),
+    "gol_batch_clear": (ctypes.c_int, [vp]),
+    "gol_batch_step": (ctypes.c_int, [vp, i64]),
+    "gol_batch_step_timed": (ctypes.c_int, [vp, i64, ctypes.POINTER(ctypes.c_double)]),
+    "gol_batch_step_trace": (ctypes.c_int, [vp, i64, i64, u32p, i64]),
+    "gol_batch_generation": (ctypes.c_int, [vp, i64p]),
+    "gol_batch_populations": (ctypes.c_int, [vp, i64p, i64]),
+    "gol_batch_hashes": (ctypes.c_int, [vp, u64p, i64]),
+    "gol_batch_render_gray8": (ctypes.c_int, [vp, i64, u8p, i64, ctypes.c_uint8]),
+    "gol_batch_synchronize": (ctypes.c_int, [vp]),
     # test and A/B knobs (csrc/gol_debug.h: internal, not part of the gol.h boundary)
+    "gol_debug_batch_group_waves": (ctypes.c_int, [vp, ctypes.c_int]),
     "gol_debug_set_option": (ctypes.c_int, [vp, ctypes.c_char_p, i64]),
     "gol_debug_get_option": (ctypes.c_int, [vp, ctypes.c_char_p, i64p]),
     "gol_debug_option_names": (ctypes.c_char_p, []),
@@ -325,6 +344,12 @@ def device_count() -> int:
     n = ctypes.c_int()
     check(load().gol_device_count(ctypes.byref(n)), "gol_device_count")
     return n.value
+
+
+def batch_supported(width: int, height: int) -> int:
+    """gol_batch_supported: rows per lane (1..4) of a width x height board in a BoardBatch, 0 when a batch does not
+    take the geometry.  Host-only."""
+    return int(load().gol_batch_supported(width, height))
 
 
 def exchange_plan(height: int, boundary: int, nparts: int, ghost: int, k: int) -> list:

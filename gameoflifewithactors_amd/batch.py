@@ -1,0 +1,156 @@
+"""BoardBatch: many independent small boards of one size, stepped together.
+
+Reference seam: the reference's board is 100 x 100 and seeded from ``DateTime.Now.Ticks``
+(``GameOfLifeLogic.fs:5``, ``GameOfLifeDriver.fs:9-11``), so every run of the app is another member of one ensemble.
+One ``BoardBatch`` holds ``count`` such boards bit-packed in HBM and ``step(g)`` advances all of them ``g`` generations
+in ONE launch, one wavefront per board (``csrc/gol_batch.hip``) -- where a ``Board`` per seed would
+step them one single-wave launch after another.  ``step_trace`` samples every board's population inside that launch:
+population curves, extinction times and soup censuses over thousands of seeds are one call.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+
+from . import _lib
+from ._lib import INIT_DOTNET_MOD2, TORUS, batch_supported, check
+
+__all__ = ["BoardBatch", "batch_supported"]
+
+
+def _u8p(a: np.ndarray):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
+
+
+class BoardBatch:
+    """``count`` boards of width x height on the current HIP device.
+
+    The geometry is the single-wave pass's: 3 <= width <= 128 and ``batch_supported(width, height) > 0`` (1 to 4 rows
+    per lane on at most 64 lanes); anything else raises NotImplementedError.  boundary: ``TORUS`` or ``BOUNDED``.
+    Cell arrays are ``(n, height, width)`` uint8, nonzero = alive.
+    """
+
+    def __init__(self, width: int, height: int, count: int, boundary: int = TORUS):
+        self._lib = _lib.load()
+        h = ctypes.c_void_p()
+        check(self._lib.gol_batch_create(width, height, boundary, count, ctypes.byref(h)), "gol_batch_create")
+        self._h = h
+        _lib.hold(self)
+        self.width, self.height, self.count, self.boundary = width, height, count, boundary
+
+    # ---------------------------------------------------------------- lifetime
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None and self._h.value:
+            check(self._lib.gol_batch_destroy(self._h), "gol_batch_destroy")
+            self._h = None
+            _lib.release(self)
+
+    def __enter__(self) -> "BoardBatch":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self) -> int:
+        return self.count
+
+    # ---------------------------------------------------------------- I/O
+    def set_cells(self, cells, first: int = 0) -> "BoardBatch":
+        """Replace boards [first, first + n) with an (n, height, width) array (a single (height, width) board is n = 1)."""
+        a = np.ascontiguousarray(np.asarray(cells, dtype=np.uint8))
+        if a.ndim == 2:
+            a = a[None]
+        if a.ndim != 3 or a.shape[1:] != (self.height, self.width):
+            raise ValueError(f"cells must be (n, {self.height}, {self.width}), got {a.shape}")
+        check(self._lib.gol_batch_set_cells(self._h, first, a.shape[0], _u8p(a), a.size), "gol_batch_set_cells")
+        return self
+
+    def get_cells(self, first: int = 0, n: int | None = None) -> np.ndarray:
+        """Boards [first, first + n) (to the end by default) as an (n, height, width) uint8 array of 0 / 1."""
+        n = self.count - first if n is None else n
+        out = np.empty((max(n, 0), self.height, self.width), dtype=np.uint8)
+        check(self._lib.gol_batch_get_cells(self._h, first, n, _u8p(out), out.size), "gol_batch_get_cells")
+        return out
+
+    def render_gray8(self, board: int, alive_value: int = 128, stride: int | None = None) -> np.ndarray:
+        """Gray8 frame of one board, pixels[x + y*stride] (Board.render_gray8)."""
+        stride = self.width if stride is None else stride
+        out = np.empty(max(stride, 0) * self.height, dtype=np.uint8)
+        check(self._lib.gol_batch_render_gray8(self._h, board, _u8p(out), stride, alive_value),
+              "gol_batch_render_gray8")
+        return out
+
+    # ---------------------------------------------------------------- seeding
+    def seed_dotnet(self, seeds, mode: int = INIT_DOTNET_MOD2) -> "BoardBatch":
+        """Board i <- System.Random(seeds[i]) as the reference uses it (Board.seed_dotnet); len(seeds) == count."""
+        a = np.ascontiguousarray(np.asarray(seeds, dtype=np.int32)).reshape(-1)
+        check(self._lib.gol_batch_seed_dotnet(self._h, a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), a.size, mode),
+              "gol_batch_seed_dotnet")
+        return self
+
+    def seed_splitmix(self, seed: int) -> "BoardBatch":
+        """Board i <- the cells Board.seed_splitmix(seed + i) gives a single board of this size."""
+        check(self._lib.gol_batch_seed_splitmix(self._h, seed & 0xFFFFFFFFFFFFFFFF), "gol_batch_seed_splitmix")
+        return self
+
+    def clear(self) -> "BoardBatch":
+        check(self._lib.gol_batch_clear(self._h), "gol_batch_clear")
+        return self
+
+    # ---------------------------------------------------------------- stepping
+    def step(self, generations: int = 1) -> "BoardBatch":
+        check(self._lib.gol_batch_step(self._h, generations), "gol_batch_step")
+        return self
+
+    def step_timed(self, generations: int) -> float:
+        """gol_batch_step between HIP timing events on the batch's stream, synchronised: microseconds of device time."""
+        us = ctypes.c_double()
+        check(self._lib.gol_batch_step_timed(self._h, generations, ctypes.byref(us)), "gol_batch_step_timed")
+        return us.value
+
+    def step_trace(self, generations: int, every: int = 1) -> np.ndarray:
+        """Advance `generations` (a multiple of `every`) and return the (generations // every, count) uint32 populations
+        after every `every`-th generation of this call, sampled inside the one launch."""
+        t = max(generations, 0) // every if every >= 1 else 0  # (the library refuses what does not divide)
+        out = np.empty((t, self.count), dtype=np.uint32)
+        check(self._lib.gol_batch_step_trace(self._h, generations, every, out.ctypes.data_as(_lib.u32p), out.size),
+              "gol_batch_step_trace")
+        return out
+
+    def synchronize(self) -> None:
+        check(self._lib.gol_batch_synchronize(self._h), "gol_batch_synchronize")
+
+    @property
+    def generation(self) -> int:
+        v = ctypes.c_int64()
+        check(self._lib.gol_batch_generation(self._h, ctypes.byref(v)), "gol_batch_generation")
+        return v.value
+
+    # ---------------------------------------------------------------- observables
+    def populations(self) -> np.ndarray:
+        """(count,) int64: live cells of every board."""
+        out = np.empty(self.count, dtype=np.int64)
+        check(self._lib.gol_batch_populations(self._h, out.ctypes.data_as(_lib.i64p), out.size),
+              "gol_batch_populations")
+        return out
+
+    def hashes(self) -> np.ndarray:
+        """(count,) uint64: the canonical hash of every board (Board.hash of a single board with the same cells)."""
+        out = np.empty(self.count, dtype=np.uint64)
+        check(self._lib.gol_batch_hashes(self._h, out.ctypes.data_as(_lib.u64p), out.size), "gol_batch_hashes")
+        return out
+
+    def info(self) -> dict:
+        w, h, c = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        b = ctypes.c_int()
+        check(self._lib.gol_batch_info(self._h, ctypes.byref(w), ctypes.byref(h), ctypes.byref(b), ctypes.byref(c)),
+              "gol_batch_info")
+        return {"width": w.value, "height": h.value, "boundary": b.value, "count": c.value,
+                "rows_per_lane": batch_supported(w.value, h.value)}

@@ -1,0 +1,249 @@
+// gol_batch.hip -- a batch of small boards, one wavefront per board, any number of boards per launch (gfx950).
+//
+// The reference's board is 100 x 100, seeded from the clock (GameOfLifeLogic.fs:5, GameOfLifeDriver.fs:9-11): every run
+// is another member of one ensemble.  The single-wave pass (gol_wave.hip) steps one such board on one of the chip's
+// 1024 SIMDs; here `count` boards of one geometry are stepped by `count` waves in one launch, each wave alone with its
+// board: it loads the board into registers, runs every generation of the call there (gol_wave_body.h: the arithmetic
+// of the single-wave pass, no barrier, no memory traffic) and stores it back to the same place.
+//
+// Layout: boards back to back, board i row y = NW = ceil(W / 32) words at words[(i * H + y) * NW], bit b of word j =
+// cell 32 j + b, bits at or beyond W zero.  In place: a wave reads its whole board before it writes any of it, and no
+// wave touches another board.  Geometry: the single-wave pass's (wave_resident_rpl: W 3..128, 1..4 rows per lane on at
+// most 64 lanes).
+#include "gol_batch_host.h"
+#include "gol_internal.h"
+#include "gol_wave_body.h"
+
+namespace gol {
+namespace {
+
+// Sum of v over the wave's 64 lanes, the same value in every lane: four DPP adds leave every lane of a row of 16 with
+// the row's sum (quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror, row_mirror), then the four rows' sums are
+// read as scalars.  Every lane of the wave must be executing.
+template <int CTRL>
+__device__ __forceinline__ uint32_t dpp_read(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, true);
+}
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
+    v += dpp_read<0xB1>(v);
+    v += dpp_read<0x4E>(v);
+    v += dpp_read<0x141>(v);
+    v += dpp_read<0x140>(v);
+    return (uint32_t)__builtin_amdgcn_readlane((int)v, 0) + (uint32_t)__builtin_amdgcn_readlane((int)v, 16) +
+           (uint32_t)__builtin_amdgcn_readlane((int)v, 32) + (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
+}
+
+// Board `blockIdx.x * waves per group + wave` runs `samples` x `every` generations.  TRACE: after each `every`
+// generations the board's population goes to trace[t * count + board] (t = 0 .. samples - 1); otherwise samples is 1
+// and trace unused.  A wave past the last board leaves before it touches memory.
+template <int NW, int RPL, bool BOUNDED, bool TRACE>
+__global__ __launch_bounds__(256) void gol_batch_step(uint32_t* __restrict__ words, int64_t count, int W, int H,
+                                                      int samples, int64_t every, uint32_t* __restrict__ trace) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t board = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave;
+    if (board >= count) return;
+    const int nl = H / RPL;  // active lanes
+    const bool active = lane < nl;
+    uint32_t* rows = words + (board * H + lane * RPL) * NW;  // this lane's RPL * NW words
+    uint32_t w[RPL][NW];
+#pragma unroll
+    for (int i = 0; i < RPL; i++)
+#pragma unroll
+        for (int j = 0; j < NW; j++) w[i][j] = 0;
+    if (active) {  // (an inactive lane's `rows` points past its board: never dereferenced)
+#pragma unroll
+        for (int i = 0; i < RPL; i++)
+#pragma unroll
+            for (int j = 0; j < NW; j++) w[i][j] = rows[i * NW + j];
+    }
+    const WaveGeom geom = wave_geom<BOUNDED>(W, nl, lane);
+
+    for (int t = 0; t < samples; t++) {
+        for (int64_t g = 0; g < every; g++) wave_generation<NW, RPL, BOUNDED>(w, geom);
+        if (TRACE) {
+            // lanes past the last active one hold whatever the arithmetic left there: they count as 0
+            uint32_t pop = 0;
+#pragma unroll
+            for (int i = 0; i < RPL; i++)
+#pragma unroll
+                for (int j = 0; j < NW; j++) pop += __popc(w[i][j]);
+            pop = wave_sum_u32(active ? pop : 0u);
+            if (lane == 0) trace[(int64_t)t * count + board] = pop;
+        }
+    }
+
+    if (!active) return;
+#pragma unroll
+    for (int i = 0; i < RPL; i++)
+#pragma unroll
+        for (int j = 0; j < NW; j++) rows[i * NW + j] = w[i][j];
+}
+
+__device__ __forceinline__ uint64_t mix64(uint64_t k) {  // the hash's fmix64 (gol_formats.hip)
+    k ^= k >> 33;
+    k *= 0xff51afd7ed558ccdULL;
+    k ^= k >> 33;
+    k *= 0xc4ceb9fe1a85ec53ULL;
+    k ^= k >> 33;
+    return k;
+}
+
+// One wave per board: out[2 i] = population of board i, out[2 i + 1] = its canonical hash partial sum (the board
+// hash's definition on 64-cell chunks, DESIGN.md: chunk j of row y has key y * ceil(W / 64) + j, from 0 for each
+// board; gol_hash_finalize(partial, W, H) on the host makes it the hash of a single board with these cells).
+__global__ __launch_bounds__(256) void gol_batch_observe(const uint32_t* __restrict__ words, int64_t count, int W,
+                                                         int H, unsigned long long* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const int64_t board = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (board >= count) return;
+    const int nw = (W + 31) / 32, nc = (W + 63) / 64;
+    const uint32_t* b = words + board * H * nw;
+    uint64_t pop = 0, sum = 0;
+    for (int idx = lane; idx < nc * H; idx += 64) {
+        const int j = idx % nc, y = idx / nc;
+        const uint64_t lo = b[y * nw + 2 * j];
+        const uint64_t hi = 2 * j + 1 < nw ? b[y * nw + 2 * j + 1] : 0u;
+        const uint64_t v = lo | (hi << 32);
+        pop += __popcll(v);
+        sum += mix64(v ^ mix64((uint64_t)idx + 0x9E3779B97F4A7C15ULL));
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        pop += __shfl_down(pop, off, 64);
+        sum += __shfl_down(sum, off, 64);
+    }
+    if (lane == 0) {
+        out[2 * board] = pop;
+        out[2 * board + 1] = sum;
+    }
+}
+
+// bytes -> words, one thread per word: `rows` rows of W cells (boards back to back are simply more rows)
+__global__ void gol_batch_pack(const uint8_t* __restrict__ cells, uint32_t* __restrict__ words, int W, int nw,
+                               int64_t rows) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= rows * nw) return;
+    const int64_t r = idx / nw;
+    const int j = (int)(idx % nw);
+    const uint8_t* src = cells + r * W + 32 * j;
+    const int n = W - 32 * j < 32 ? W - 32 * j : 32;
+    uint32_t v = 0;
+    for (int b = 0; b < n; b++) v |= (uint32_t)(src[b] != 0) << b;
+    words[idx] = v;
+}
+
+// words -> bytes, one thread per cell: out[x + r * stride] = alive ? value : 0
+__global__ void gol_batch_unpack(const uint32_t* __restrict__ words, uint8_t* __restrict__ out, int W, int nw,
+                                 int64_t rows, int64_t stride, uint8_t value) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= rows * W) return;
+    const int64_t r = idx / W;
+    const int x = (int)(idx % W);
+    out[x + r * stride] = ((words[r * nw + (x >> 5)] >> (x & 31)) & 1u) ? value : (uint8_t)0;
+}
+
+__device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
+    z += 0x9E3779B97F4A7C15ULL;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+    return z ^ (z >> 31);
+}
+
+// board i <- gol_seed_splitmix(seed + i): word j of row y = low32(splitmix64((seed + i) ^ (y * nw + j))), cut at W
+__global__ void gol_batch_splitmix(uint32_t* __restrict__ words, int64_t count, int W, int H, int nw, uint64_t seed) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t per = (int64_t)H * nw;
+    if (idx >= count * per) return;
+    const int64_t board = idx / per, k = idx % per;
+    const int j = (int)(k % nw);
+    uint32_t v = (uint32_t)splitmix64((seed + (uint64_t)board) ^ (uint64_t)k);
+    if (j == nw - 1 && (W & 31)) v &= (1u << (W & 31)) - 1u;
+    words[idx] = v;
+}
+
+unsigned blocks(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
+
+template <int NW, int RPL>
+hipError_t step_nr(uint32_t* words, int64_t count, int W, int H, bool bounded, int samples, int64_t every,
+                   uint32_t* trace, int group_waves, hipStream_t s) {
+    const dim3 grid(blocks(count, group_waves)), block(64 * group_waves);
+#define GOL_BATCH_LAUNCH(B, T) \
+    hipLaunchKernelGGL((gol_batch_step<NW, RPL, B, T>), grid, block, 0, s, words, count, W, H, samples, every, trace)
+    if (bounded) {
+        if (trace)
+            GOL_BATCH_LAUNCH(true, true);
+        else
+            GOL_BATCH_LAUNCH(true, false);
+    } else {
+        if (trace)
+            GOL_BATCH_LAUNCH(false, true);
+        else
+            GOL_BATCH_LAUNCH(false, false);
+    }
+#undef GOL_BATCH_LAUNCH
+    return hipGetLastError();
+}
+
+template <int NW>
+hipError_t step_n(uint32_t* words, int64_t count, int W, int H, bool bounded, int samples, int64_t every,
+                  uint32_t* trace, int group_waves, int rpl, hipStream_t s) {
+    switch (rpl) {
+        case 1: return step_nr<NW, 1>(words, count, W, H, bounded, samples, every, trace, group_waves, s);
+        case 2: return step_nr<NW, 2>(words, count, W, H, bounded, samples, every, trace, group_waves, s);
+        case 3: return step_nr<NW, 3>(words, count, W, H, bounded, samples, every, trace, group_waves, s);
+        case 4: return step_nr<NW, 4>(words, count, W, H, bounded, samples, every, trace, group_waves, s);
+    }
+    return hipErrorInvalidValue;
+}
+
+}  // namespace
+
+hipError_t launch_batch_step(uint32_t* words, int64_t count, int64_t W, int64_t H, bool bounded, int64_t samples,
+                             int64_t every, uint32_t* trace, int group_waves, hipStream_t s) {
+    const int rpl = wave_resident_rpl(W, H);
+    if (!rpl || count < 1 || count > kBatchCountMax || samples < 1 || samples > INT32_MAX || every < 1 ||
+        (!trace && samples != 1) || (group_waves != 1 && group_waves != 4))
+        return hipErrorInvalidValue;
+    switch ((int)((W + 31) / 32)) {
+        case 1: return step_n<1>(words, count, (int)W, (int)H, bounded, (int)samples, every, trace, group_waves, rpl, s);
+        case 2: return step_n<2>(words, count, (int)W, (int)H, bounded, (int)samples, every, trace, group_waves, rpl, s);
+        case 3: return step_n<3>(words, count, (int)W, (int)H, bounded, (int)samples, every, trace, group_waves, rpl, s);
+        case 4: return step_n<4>(words, count, (int)W, (int)H, bounded, (int)samples, every, trace, group_waves, rpl, s);
+    }
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_batch_observe(const uint32_t* words, int64_t count, int64_t W, int64_t H, unsigned long long* out,
+                                hipStream_t s) {
+    if (!wave_resident_rpl(W, H) || count < 1 || count > kBatchCountMax) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(gol_batch_observe, dim3(blocks(count, 4)), dim3(256), 0, s, words, count, (int)W, (int)H, out);
+    return hipGetLastError();
+}
+
+// rows <= 2^30 keeps both grids below 2^31 workgroups
+hipError_t launch_batch_pack(const uint8_t* cells, uint32_t* words, int64_t W, int64_t rows, hipStream_t s) {
+    if (W < 1 || W > 128 || rows < 1 || rows > ((int64_t)1 << 30)) return hipErrorInvalidValue;
+    const int nw = (int)((W + 31) / 32);
+    hipLaunchKernelGGL(gol_batch_pack, dim3(blocks(rows * nw, 256)), dim3(256), 0, s, cells, words, (int)W, nw, rows);
+    return hipGetLastError();
+}
+
+hipError_t launch_batch_unpack(const uint32_t* words, uint8_t* out, int64_t W, int64_t rows, int64_t stride,
+                               uint8_t value, hipStream_t s) {
+    if (W < 1 || W > 128 || rows < 1 || rows > ((int64_t)1 << 30) || stride < W) return hipErrorInvalidValue;
+    const int nw = (int)((W + 31) / 32);
+    hipLaunchKernelGGL(gol_batch_unpack, dim3(blocks(rows * W, 256)), dim3(256), 0, s, words, out, (int)W, nw, rows,
+                       stride, value);
+    return hipGetLastError();
+}
+
+hipError_t launch_batch_splitmix(uint32_t* words, int64_t count, int64_t W, int64_t H, uint64_t seed, hipStream_t s) {
+    if (!wave_resident_rpl(W, H) || count < 1 || count > kBatchCountMax) return hipErrorInvalidValue;
+    const int nw = (int)((W + 31) / 32);
+    hipLaunchKernelGGL(gol_batch_splitmix, dim3(blocks(count * H * nw, 256)), dim3(256), 0, s, words, count, (int)W,
+                       (int)H, nw, seed);
+    return hipGetLastError();
+}
+
+}  // namespace gol

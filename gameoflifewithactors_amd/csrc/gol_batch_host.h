@@ -1,0 +1,56 @@
+// gol_batch_host.h -- the host-only arithmetic of the batch handle (gol_batch.cpp): argument ranges and the .NET
+// seeding of packed boards.  No HIP here, so tests/cpp/test_batch_host.cpp compiles it alone under the address and
+// undefined-behaviour sanitizers.
+#pragma once
+#include <stdint.h>
+
+#include "gol_seed_rle.h"
+
+namespace gol {
+
+constexpr int64_t kBatchCountMax = (int64_t)1 << 22;  // boards per batch
+constexpr int64_t kBatchTraceMax = (int64_t)1 << 26;  // entries of one gol_batch_step_trace call
+
+// Rows per lane of the single-wave geometry: the fewest (1..4) that divide H with at most 64 lanes, for W in 3..128;
+// 0 otherwise (gol_wave.hip wave_resident_rpl states the same rule for the kernels).
+inline int batch_rpl(int64_t W, int64_t H) {
+    if (W < 3 || W > 128 || H < 3) return 0;
+    for (int r = 1; r <= 4; r++)
+        if (H % r == 0 && H / r <= 64) return r;
+    return 0;
+}
+
+// Boards [first, first + n) lie inside [0, count) and `len` is their n * cells bytes (n >= 1; no overflow for any input).
+inline bool batch_range_ok(int64_t first, int64_t n, int64_t count, int64_t len, int64_t cells) {
+    if (first < 0 || n < 1 || first >= count || n > count - first) return false;
+    return len == n * cells;  // n <= 2^22 and cells <= 2^15
+}
+
+// A trace call: generations >= 0 a multiple of every >= 1, generations / every samples of `count` entries each, at most
+// kBatchTraceMax in all, len exactly that many.  *samples is set when the call is valid.
+inline bool batch_trace_ok(int64_t generations, int64_t every, int64_t count, int64_t len, int64_t* samples,
+                           const char** why) {
+    if (generations < 0) return *why = "generations must be >= 0", false;
+    if (every < 1) return *why = "every must be >= 1", false;
+    if (generations % every) return *why = "generations must be a multiple of every", false;
+    const int64_t t = generations / every;
+    if (t > kBatchTraceMax / count) return *why = "more than 2^26 trace entries", false;
+    if (len != t * count) return *why = "trace length must be (generations / every) * count", false;
+    *samples = t;
+    return true;
+}
+
+// The packed rows (nw = ceil(W / 32) words each) of the board gol_seed_dotnet(seed, mode) makes: creation order x outer,
+// y inner (GameOfLifeDriver.fs:16-19; Array2D.init in Script.fsx:27); mode 0: Next() % 2 = 0, mode 1: Next(2) = 0.
+inline void batch_seed_dotnet_words(int32_t seed, int mode, int64_t W, int64_t H, uint32_t* words) {
+    const int64_t nw = (W + 31) / 32;
+    for (int64_t k = 0; k < nw * H; k++) words[k] = 0;
+    DotNetRandom r(seed);
+    for (int64_t x = 0; x < W; x++)
+        for (int64_t y = 0; y < H; y++) {
+            const bool alive = mode == 0 ? (r.Next() % 2 == 0) : (r.Next(2) == 0);
+            if (alive) words[y * nw + (x >> 5)] |= 1u << (x & 31);
+        }
+}
+
+}  // namespace gol

@@ -39,6 +39,9 @@ const char* gol_debug_option_names(void);
 int gol_debug_pipe_plan(const gol_strip* s, int k, int64_t out_begin, int64_t out_end, int64_t wgs, int64_t* plan,
                         int64_t n);
 int gol_debug_pipe_errors(int* out);
+/* Batch handle (gol_batch.hip): boards (wavefronts) per workgroup of its step launches, 1 (the default) or 4 -- the
+ * workgroup-shape A/B of DESIGN.md 4.9.  Results are identical. */
+int gol_debug_batch_group_waves(gol_batch* b, int waves);
 
 #ifdef __cplusplus
 }

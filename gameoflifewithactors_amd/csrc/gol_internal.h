@@ -238,4 +238,22 @@ int wave_resident_rpl(int64_t W, int64_t H);  // rows per lane, 0 = the board do
 hipError_t launch_wave_resident(const void* src, void* dst, int64_t W, int64_t H, int64_t pitch, int64_t gens,
                                 bool bounded, bool bytes, hipStream_t s);
 
+// ---- gol_batch.hip: `count` boards of one single-wave geometry (wave_resident_rpl) back to back, NW = ceil(W / 32)
+// words per row, bits past W zero; one wavefront per board; count <= kBatchCountMax (gol_batch_host.h)
+// samples x every generations of every board, in place.  trace == nullptr: samples must be 1; otherwise
+// trace[t * count + i] = population of board i after (t + 1) * every generations.  group_waves: boards (waves) per
+// workgroup, 1 or 4.
+hipError_t launch_batch_step(uint32_t* words, int64_t count, int64_t W, int64_t H, bool bounded, int64_t samples,
+                             int64_t every, uint32_t* trace, int group_waves, hipStream_t s);
+// out[2 i] = population, out[2 i + 1] = canonical hash partial sum of board i (gol_hash_finalize(partial, W, H))
+hipError_t launch_batch_observe(const uint32_t* words, int64_t count, int64_t W, int64_t H, unsigned long long* out,
+                                hipStream_t s);
+// `rows` rows (of any number of boards) between one byte per cell and the packed rows; unpack writes value / 0 at
+// out[x + r * stride]
+hipError_t launch_batch_pack(const uint8_t* cells, uint32_t* words, int64_t W, int64_t rows, hipStream_t s);
+hipError_t launch_batch_unpack(const uint32_t* words, uint8_t* out, int64_t W, int64_t rows, int64_t stride,
+                               uint8_t value, hipStream_t s);
+// board i <- the cells gol_seed_splitmix(seed + i) gives a single W x H board
+hipError_t launch_batch_splitmix(uint32_t* words, int64_t count, int64_t W, int64_t H, uint64_t seed, hipStream_t s);
+
 }  // namespace gol

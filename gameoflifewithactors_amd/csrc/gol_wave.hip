@@ -17,36 +17,10 @@
 // and to the board's own storage: bytes (ragged widths, one byte per cell) or packed ilv-1 words.
 #include "gol_internal.h"
 #include "gol_bitlogic.h"
+#include "gol_wave_body.h"
 
 namespace gol {
 namespace {
-
-__device__ __forceinline__ uint32_t bperm(int byte_addr, uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_ds_bpermute(byte_addr, (int)v);
-}
-
-// Horizontal 3-sums of one ragged row (NW words, last word holding bits [0, lb]).
-template <int NW, bool BOUNDED>
-__device__ __forceinline__ void ragged_row_sum(const uint32_t (&w)[NW], int lb, uint32_t lbbit, uint32_t (&s)[NW],
-                                               uint32_t (&c)[NW]) {
-    // west neighbour of cell 0 is cell W-1 (bit lb of the last word), moved to bit 31 of a carry word
-    const uint32_t wcarry = BOUNDED ? 0u : w[NW - 1] << (31 - lb);
-    uint32_t west[NW], east[NW];
-#pragma unroll
-    for (int j = 0; j < NW; j++) west[j] = align_right(w[j], j == 0 ? wcarry : w[j - 1], 31);
-#pragma unroll
-    for (int j = 0; j + 1 < NW; j++) east[j] = align_right(w[j + 1], w[j], 1);
-    // east neighbour of cell W-1 is cell 0: bit 0 of word 0 into bit lb of the last word
-    if (BOUNDED)
-        east[NW - 1] = w[NW - 1] >> 1;
-    else
-        east[NW - 1] = lut3<0xEA>(w[NW - 1] >> 1, w[0] << lb, lbbit);  // a | (b & c)
-#pragma unroll
-    for (int j = 0; j < NW; j++) {
-        s[j] = lut3<0x96>(west[j], w[j], east[j]);
-        c[j] = lut3<0xE8>(west[j], w[j], east[j]);
-    }
-}
 
 template <int NW, int RPL, bool BOUNDED, bool BYTES>
 __global__ __launch_bounds__(64) void gol_wave_resident(const void* __restrict__ src, void* __restrict__ dst, int W,
@@ -54,9 +28,6 @@ __global__ __launch_bounds__(64) void gol_wave_resident(const void* __restrict__
     const int lane = threadIdx.x;
     const int nl = H / RPL;  // active lanes
     const bool active = lane < nl;
-    const int lb = (W - 1) & 31;
-    const uint32_t lbbit = 1u << lb;
-    const uint32_t lastmask = lb == 31 ? 0xffffffffu : (lbbit << 1) - 1u;
     uint32_t w[RPL][NW];
 
     // ---- load the board: byte boards row by row, 64 cells per wave-wide coalesced load, packed by ballot (the
@@ -110,36 +81,9 @@ __global__ __launch_bounds__(64) void gol_wave_resident(const void* __restrict__
             for (int j = 0; j < NW; j++)
                 w[i][j] = static_cast<const uint32_t*>(src)[(int64_t)(lane * RPL + i) * pitch + j];
     }
-    // lanes the rows above the first row / below the last row come from (ds_bpermute byte addresses)
-    const int up_lane = lane == 0 ? nl - 1 : lane - 1;
-    const int dn_lane = lane + 1 >= nl ? 0 : lane + 1;
-    const int up_addr = up_lane * 4, dn_addr = dn_lane * 4;
-    const uint32_t up_mask = (BOUNDED && lane == 0) ? 0u : 0xffffffffu;  // dead rows outside a bounded board
-    const uint32_t dn_mask = (BOUNDED && lane == nl - 1) ? 0u : 0xffffffffu;
-
-    for (int g = 0; g < gens; g++) {
-        uint32_t s[RPL][NW], c[RPL][NW];
-#pragma unroll
-        for (int i = 0; i < RPL; i++) ragged_row_sum<NW, BOUNDED>(w[i], lb, lbbit, s[i], c[i]);
-        uint32_t us[NW], uc[NW], ds[NW], dc[NW];
-#pragma unroll
-        for (int j = 0; j < NW; j++) {
-            us[j] = bperm(up_addr, s[RPL - 1][j]) & up_mask;
-            uc[j] = bperm(up_addr, c[RPL - 1][j]) & up_mask;
-            ds[j] = bperm(dn_addr, s[0][j]) & dn_mask;
-            dc[j] = bperm(dn_addr, c[0][j]) & dn_mask;
-        }
-#pragma unroll
-        for (int i = 0; i < RPL; i++)
-#pragma unroll
-            for (int j = 0; j < NW; j++) {
-                const uint32_t sP = i == 0 ? us[j] : s[i - 1][j], cP = i == 0 ? uc[j] : c[i - 1][j];
-                const uint32_t sN = i == RPL - 1 ? ds[j] : s[i + 1][j], cN = i == RPL - 1 ? dc[j] : c[i + 1][j];
-                uint32_t v = life_next(sP, cP, s[i][j], c[i][j], sN, cN, w[i][j]);
-                if (j == NW - 1) v &= lastmask;
-                w[i][j] = v;
-            }
-    }
+    // lanes the rows above the first row / below the last row come from, and the generation itself: gol_wave_body.h
+    const WaveGeom geom = wave_geom<BOUNDED>(W, nl, lane);
+    for (int g = 0; g < gens; g++) wave_generation<NW, RPL, BOUNDED>(w, geom);
 
     // ---- store: byte boards row by row, each lane writing one cell of a 64-cell run (the owner lane's two
     // words read as scalars), packed boards one word store per owned word

@@ -1,0 +1,95 @@
+// gol_wave_body.h -- one generation of a board held in one wavefront's registers: the arithmetic the single-wave
+// pass (gol_wave.hip) and the batch pass (gol_batch.hip, one wave per board) share.
+//
+//   lane L holds rows L*RPL .. L*RPL + RPL-1 (RPL = rows per lane, H % RPL == 0, nl = H / RPL <= 64 active lanes),
+//   each as NW = ceil(W / 32) words, bit b of word j = cell 32 j + b, bits >= W zero.
+//
+// Lanes at or beyond nl run the same instructions on whatever they hold: no active lane reads them (a lane's upper
+// neighbour is lane - 1, or nl - 1 for lane 0; its lower one lane + 1, or 0 for lane nl - 1), and they are never
+// stored.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "gol_bitlogic.h"
+
+namespace gol {
+
+__device__ __forceinline__ uint32_t bperm(int byte_addr, uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_ds_bpermute(byte_addr, (int)v);
+}
+
+// Horizontal 3-sums of one ragged row (NW words, last word holding bits [0, lb]).
+template <int NW, bool BOUNDED>
+__device__ __forceinline__ void ragged_row_sum(const uint32_t (&w)[NW], int lb, uint32_t lbbit, uint32_t (&s)[NW],
+                                               uint32_t (&c)[NW]) {
+    // west neighbour of cell 0 is cell W-1 (bit lb of the last word), moved to bit 31 of a carry word
+    const uint32_t wcarry = BOUNDED ? 0u : w[NW - 1] << (31 - lb);
+    uint32_t west[NW], east[NW];
+#pragma unroll
+    for (int j = 0; j < NW; j++) west[j] = align_right(w[j], j == 0 ? wcarry : w[j - 1], 31);
+#pragma unroll
+    for (int j = 0; j + 1 < NW; j++) east[j] = align_right(w[j + 1], w[j], 1);
+    // east neighbour of cell W-1 is cell 0: bit 0 of word 0 into bit lb of the last word
+    if (BOUNDED)
+        east[NW - 1] = w[NW - 1] >> 1;
+    else
+        east[NW - 1] = lut3<0xEA>(w[NW - 1] >> 1, w[0] << lb, lbbit);  // a | (b & c)
+#pragma unroll
+    for (int j = 0; j < NW; j++) {
+        s[j] = lut3<0x96>(west[j], w[j], east[j]);
+        c[j] = lut3<0xE8>(west[j], w[j], east[j]);
+    }
+}
+
+// What a lane needs beside its rows: the row end, and the lanes its outer rows' neighbours come from.
+struct WaveGeom {
+    int lb;             // bit of the row's last cell in the last word, (W - 1) & 31
+    uint32_t lbbit;     // 1 << lb
+    uint32_t lastmask;  // the last word's cells
+    int up_addr, dn_addr;       // ds_bpermute byte addresses of the lanes above / below
+    uint32_t up_mask, dn_mask;  // 0 where that row lies outside a bounded board
+};
+
+template <bool BOUNDED>
+__device__ __forceinline__ WaveGeom wave_geom(int W, int nl, int lane) {
+    WaveGeom g;
+    g.lb = (W - 1) & 31;
+    g.lbbit = 1u << g.lb;
+    g.lastmask = g.lb == 31 ? 0xffffffffu : (g.lbbit << 1) - 1u;
+    const int up_lane = lane == 0 ? nl - 1 : lane - 1;
+    const int dn_lane = lane + 1 >= nl ? 0 : lane + 1;
+    g.up_addr = up_lane * 4;
+    g.dn_addr = dn_lane * 4;
+    g.up_mask = (BOUNDED && lane == 0) ? 0u : 0xffffffffu;  // dead rows outside a bounded board
+    g.dn_mask = (BOUNDED && lane == nl - 1) ? 0u : 0xffffffffu;
+    return g;
+}
+
+// One synchronous B3/S23 generation of the wave's board, in place in w.
+template <int NW, int RPL, bool BOUNDED>
+__device__ __forceinline__ void wave_generation(uint32_t (&w)[RPL][NW], const WaveGeom& g) {
+    uint32_t s[RPL][NW], c[RPL][NW];
+#pragma unroll
+    for (int i = 0; i < RPL; i++) ragged_row_sum<NW, BOUNDED>(w[i], g.lb, g.lbbit, s[i], c[i]);
+    uint32_t us[NW], uc[NW], ds[NW], dc[NW];
+#pragma unroll
+    for (int j = 0; j < NW; j++) {
+        us[j] = bperm(g.up_addr, s[RPL - 1][j]) & g.up_mask;
+        uc[j] = bperm(g.up_addr, c[RPL - 1][j]) & g.up_mask;
+        ds[j] = bperm(g.dn_addr, s[0][j]) & g.dn_mask;
+        dc[j] = bperm(g.dn_addr, c[0][j]) & g.dn_mask;
+    }
+#pragma unroll
+    for (int i = 0; i < RPL; i++)
+#pragma unroll
+        for (int j = 0; j < NW; j++) {
+            const uint32_t sP = i == 0 ? us[j] : s[i - 1][j], cP = i == 0 ? uc[j] : c[i - 1][j];
+            const uint32_t sN = i == RPL - 1 ? ds[j] : s[i + 1][j], cN = i == RPL - 1 ? dc[j] : c[i + 1][j];
+            uint32_t v = life_next(sP, cP, s[i][j], c[i][j], sN, cN, w[i][j]);
+            if (j == NW - 1) v &= g.lastmask;
+            w[i][j] = v;
+        }
+}
+
+}  // namespace gol

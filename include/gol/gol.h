@@ -244,6 +244,52 @@ int gol_pass_timing(gol_board* b, int n, double* interior_us, double* wait_us, d
 int gol_set_option(gol_board* b, const char* name, int64_t value);
 int gol_get_option(gol_board* b, const char* name, int64_t* value);
 
+/* ------------------------------------------------------------------------------------------------
+ * A batch of small boards: `count` independent boards of one geometry, stepped by ONE launch with one wavefront per
+ * board.  The reference's board is 100 x 100 and seeded from the clock (GameOfLifeLogic.fs:5,
+ * GameOfLifeDriver.fs:9-11), so every run is another member of one ensemble; a batch runs thousands of members at once
+ * where a gol_board handle per seed would step them one single-wave launch after another.
+ *   Geometry:  the single-wave pass's -- 3 <= width <= 128 and gol_batch_supported(width, height) > 0 (the fewest rows
+ *              per lane in 1..4 that divide the height with height / rows <= 64) -- anything else gol_create accepts
+ *              returns GOL_ERR_UNSUPPORTED (129 x 64, 128 x 255, 100 x 257).  Both boundaries.
+ *   Limits:    1 <= count <= 2^22; board ranges inside [0, count); exact buffer lengths; at most 2^26 trace entries per
+ *              call -- anything else returns GOL_ERR_INVALID.  Every argument is checked before any device work.
+ *   Handle:    opaque, on the calling thread's current device (no multi-GPU batches), serialised by its own mutex, with
+ *              its own stream; conventions as for gol_board (codes, gol_last_error, borrowed host buffers).
+ * Host buffers hold boards back to back, one byte per cell: cells[(i - first)*width*height + x + y*width].
+ * A new batch is all dead.  The setters (set_cells of any range, the seeds, clear) reset the generation counter. */
+typedef struct gol_batch gol_batch; /* opaque; library-owned */
+/* Host-only: rows per lane (1..4) of a width x height board in a batch, or 0 when a batch does not take it. */
+int gol_batch_supported(int64_t width, int64_t height);
+int gol_batch_create(int64_t width, int64_t height, int boundary, int64_t count, gol_batch** out);
+int gol_batch_destroy(gol_batch* b);
+int gol_batch_info(gol_batch* b, int64_t* width, int64_t* height, int* boundary, int64_t* count);
+/* Boards [first, first + n), n >= 1; len == n*width*height.  get_cells writes 0 / 1. */
+int gol_batch_set_cells(gol_batch* b, int64_t first, int64_t n, const uint8_t* cells, int64_t len);
+int gol_batch_get_cells(gol_batch* b, int64_t first, int64_t n, uint8_t* cells, int64_t len);
+/* n == count; board i gets the cells gol_seed_dotnet(seeds[i], mode) gives a single board of this size. */
+int gol_batch_seed_dotnet(gol_batch* b, const int32_t* seeds, int64_t n, int mode);
+/* Board i gets the cells gol_seed_splitmix(seed + i) gives a single board of this size. */
+int gol_batch_seed_splitmix(gol_batch* b, uint64_t seed);
+int gol_batch_clear(gol_batch* b);
+/* Every board advances `generations` (>= 0; 0 is a no-op) synchronous B3/S23 generations in one launch: a wavefront
+ * loads its board, runs every generation in registers and stores it.  Asynchronous; any readback synchronises. */
+int gol_batch_step(gol_batch* b, int64_t generations);
+/* As gol_batch_step between two HIP timing events on the batch's stream, synchronised: the call's device time. */
+int gol_batch_step_timed(gol_batch* b, int64_t generations, double* elapsed_us);
+/* As gol_batch_step, sampling every board's population inside the launch: every >= 1, generations % every == 0,
+ * len == (generations / every) * count <= 2^26; trace[t*count + i] = population of board i after generation
+ * every*(t + 1) of this call.  A refused call leaves the boards and the generation counter untouched. */
+int gol_batch_step_trace(gol_batch* b, int64_t generations, int64_t every, uint32_t* trace, int64_t len);
+int gol_batch_generation(gol_batch* b, int64_t* out);
+/* n == count; out[i] = population / canonical hash of board i -- the gol_population / gol_hash of a single board
+ * holding the same cells. */
+int gol_batch_populations(gol_batch* b, int64_t* out, int64_t n);
+int gol_batch_hashes(gol_batch* b, uint64_t* out, int64_t n);
+/* One board's frame, as gol_render_gray8: pixels[x + y*stride] = alive ? alive_value : 0, stride >= width. */
+int gol_batch_render_gray8(gol_batch* b, int64_t board, uint8_t* pixels, int64_t stride, uint8_t alive_value);
+int gol_batch_synchronize(gol_batch* b);
+
 const char* gol_last_error(void);
 const char* gol_version(void);
 /* 1 if a device reporting this hipDeviceProp_t::gcnArchName ("gfx950", "gfx950:sramecc+:xnack-") runs this

@@ -69,6 +69,84 @@ void applyGrid(F&& f, Grid g = grid) {           // L13-15: x outer, y inner
         for (int y = 0; y < g.Height; y++) f(x, y);
 }
 
+// ---------------------------------------------------------------- a batch of small boards (gol.h gol_batch_*)
+// `count` independent boards of one single-wave geometry, one wavefront per board, all stepped by one launch: the
+// ensemble the reference samples one clock seed at a time (GameOfLifeDriver.fs:9-11).  Cells: boards back to back,
+// cells[i*W*H + x + y*W].
+class Batch {
+   public:
+    Batch(int64_t width, int64_t height, int64_t count, int boundary = GOL_TORUS) : w_(width), h_(height), n_(count) {
+        check(gol_batch_create(width, height, boundary, count, &b_), "gol_batch_create");
+    }
+    ~Batch() {
+        if (b_) gol_batch_destroy(b_);
+    }
+    Batch(const Batch&) = delete;
+    Batch& operator=(const Batch&) = delete;
+    Batch(Batch&& o) noexcept : b_(std::exchange(o.b_, nullptr)), w_(o.w_), h_(o.h_), n_(o.n_) {}
+
+    int64_t width() const { return w_; }
+    int64_t height() const { return h_; }
+    int64_t count() const { return n_; }
+    Batch& seedDotnet(const std::vector<int32_t>& seeds, int mode = GOL_INIT_DOTNET_MOD2) {
+        check(gol_batch_seed_dotnet(b_, seeds.data(), (int64_t)seeds.size(), mode), "gol_batch_seed_dotnet");
+        return *this;
+    }
+    Batch& seedSplitmix(uint64_t seed) {
+        check(gol_batch_seed_splitmix(b_, seed), "gol_batch_seed_splitmix");
+        return *this;
+    }
+    Batch& clear() {
+        check(gol_batch_clear(b_), "gol_batch_clear");
+        return *this;
+    }
+    Batch& setCells(const std::vector<uint8_t>& cells, int64_t first = 0) {  // cells.size() / (W*H) boards
+        check(gol_batch_set_cells(b_, first, (int64_t)cells.size() / (w_ * h_), cells.data(), (int64_t)cells.size()),
+              "gol_batch_set_cells");
+        return *this;
+    }
+    std::vector<uint8_t> getCells(int64_t first, int64_t n) const {
+        std::vector<uint8_t> c(n > 0 ? (size_t)(n * w_ * h_) : 0);
+        check(gol_batch_get_cells(b_, first, n, c.data(), (int64_t)c.size()), "gol_batch_get_cells");
+        return c;
+    }
+    Batch& step(int64_t generations = 1) {
+        check(gol_batch_step(b_, generations), "gol_batch_step");
+        return *this;
+    }
+    // trace[t*count + i] = population of board i after generation every*(t + 1) of this call
+    std::vector<uint32_t> stepTrace(int64_t generations, int64_t every = 1) {
+        std::vector<uint32_t> t(generations > 0 && every > 0 ? (size_t)(generations / every * n_) : 0);
+        check(gol_batch_step_trace(b_, generations, every, t.data(), (int64_t)t.size()), "gol_batch_step_trace");
+        return t;
+    }
+    int64_t generation() const {
+        int64_t g = 0;
+        check(gol_batch_generation(b_, &g), "gol_batch_generation");
+        return g;
+    }
+    std::vector<int64_t> populations() const {
+        std::vector<int64_t> p((size_t)n_);
+        check(gol_batch_populations(b_, p.data(), n_), "gol_batch_populations");
+        return p;
+    }
+    std::vector<uint64_t> hashes() const {
+        std::vector<uint64_t> p((size_t)n_);
+        check(gol_batch_hashes(b_, p.data(), n_), "gol_batch_hashes");
+        return p;
+    }
+    std::vector<uint8_t> renderGray8(int64_t board, uint8_t alive_value = 128) const {
+        std::vector<uint8_t> p((size_t)(w_ * h_));
+        check(gol_batch_render_gray8(b_, board, p.data(), w_, alive_value), "gol_batch_render_gray8");
+        return p;
+    }
+    void synchronize() { check(gol_batch_synchronize(b_), "gol_batch_synchronize"); }
+
+   private:
+    gol_batch* b_ = nullptr;
+    int64_t w_, h_, n_;
+};
+
 // ---------------------------------------------------------------- the board (replaces the cell agents)
 class Board {
    public:
