@@ -460,6 +460,7 @@ int gol_destroy(gol_board* b) {
 int gol_set_cells(gol_board* b, const uint8_t* cells, int64_t len) {
     return with_board(b, [&] {
         if (!cells || len != b->W * b->H) return fail(GOL_ERR_INVALID, "cells length must be width*height");
+        b->generation = 0;  // a new board, as after every other setter (gol.h)
         return set_cells_impl(b, cells);
     });
 }

@@ -121,6 +121,11 @@ int strip_step_opts(const gol_strip* s, const uint32_t* src, uint32_t* dst, int 
         if (lo < -s->ghost || hi > s->rows + s->ghost)
             return fail(GOL_ERR_INVALID, "pass reads rows outside the buffer: ghost must be >= k");
     }
+    // a lane moves its block (ilv words) as one 4 * ilv-byte load, store or LDS-DMA: rows start on that boundary when
+    // the buffers do (the pitch is a multiple of ilv)
+    const uintptr_t block_bytes = 4 * (uintptr_t)s->ilv;
+    if ((uintptr_t)src % block_bytes || (uintptr_t)dst % block_bytes)
+        return fail(GOL_ERR_INVALID, "src and dst must be aligned to 4 * ilv bytes");
     gol::StreamArgs a = strip_args(s, out_begin, out_end, split_opt, seg_opt, seam_opt, split2_opt);
     GOL_HIP(gol::launch_stream_step(src, dst, a, k, s->boundary == GOL_BOUNDED, s->wrap_rows != 0, stream));
     return GOL_OK;

@@ -98,7 +98,8 @@ int gol_transport(gol_board* b, int* transport, char* note, int64_t note_len);
 int gol_destroy(gol_board* b);
 
 /* Board I/O: cells[x + y*width], len == width*height.  Replaces createCell's `alive` argument
- * (GameOfLifeLogic.fs:39) and, on readback, the per-cell Update(alive, location) stream (L64). */
+ * (GameOfLifeLogic.fs:39) and, on readback, the per-cell Update(alive, location) stream (L64).  gol_set_cells, like
+ * every call that replaces the whole board (the seeds, gol_load_packed, gol_clear), resets the generation counter. */
 int gol_set_cells(gol_board* b, const uint8_t* cells, int64_t len);
 int gol_get_cells(gol_board* b, uint8_t* cells, int64_t len);
 /* Read a window (x, y, w, h) of the board (no wrap; must lie inside): out[i + j*w] = cell (x+i, y+j). */
@@ -136,7 +137,8 @@ int gol_synchronize(gol_board* b);
 int gol_step_timed(gol_board* b, int64_t generations, double* elapsed_us);
 
 /* Replaces the render agent's pixel fill (GameOfLifeUI.fs:24-28; GameofLife.fs:53-57; Script.fsx:33-35):
- * pixels[x + y*stride] = alive ? alive_value : 0, stride >= width, buffer >= stride*height bytes. */
+ * pixels[x + y*stride] = alive ? alive_value : 0, stride >= width, buffer >= stride*height bytes; the bytes between
+ * width and stride of every row are set to 0 (all stride*height bytes are written, none beyond them). */
 int gol_render_gray8(gol_board* b, uint8_t* pixels, int64_t stride, uint8_t alive_value);
 
 /* A zoomable view of the board: what the render agent shows (GameOfLifeUI.fs:21-31) for boards no screen holds at one
@@ -320,7 +322,14 @@ typedef struct gol_strip {
 } gol_strip;
 
 /* k generations over owned rows [out_begin, out_end) from src to dst (distinct buffers, same geometry).
- * Reads rows [out_begin-k, out_end+k); with wrap_rows = 0 those must lie in [-ghost, rows+ghost). */
+ * Reads rows [out_begin-k, out_end+k); with wrap_rows = 0 those must lie in [-ghost, rows+ghost), except that rows
+ * beyond a bounded board's edge are dead whatever the buffer holds there (they need not exist: a bounded board in one
+ * strip has ghost = 0).  The result depends on the first width/32 words of those rows only, and only the first
+ * width/32 words of dst's rows [out_begin, out_end) are written: pad words (pitch > width/32, any multiple of ilv),
+ * every other row of dst and all of src are left as they are.  src and dst must be aligned to 4 * ilv bytes (a lane
+ * moves its block of ilv words as one load, store or LDS-DMA; any device allocation is aligned to 256) -- anything
+ * else returns GOL_ERR_INVALID.  The other gol_strip_* calls move single words and take any word-aligned buffer;
+ * they, too, read and write the first width/32 words of the owned rows only. */
 int gol_strip_step(const gol_strip* s, const uint32_t* src, uint32_t* dst, int k, int64_t out_begin,
                    int64_t out_end, void* stream);
 int gol_strip_seed_splitmix(const gol_strip* s, uint32_t* buf, uint64_t seed, void* stream);

@@ -11,29 +11,7 @@ import numpy as np
 import torch
 
 import gol_oracle as o
-
-
-def _cell_of_bit(width: int, ilv: int) -> np.ndarray:
-    """For every stored bit position p = 32*w + b of a row: the cell it holds (include/gol/gol.h layout:
-    block k of ilv words, word j bit b = cell 32*ilv*k + j + ilv*b)."""
-    p = np.arange(width)
-    w, b = p // 32, p % 32
-    return (w // ilv) * 32 * ilv + (w % ilv) + ilv * b
-
-
-def _unpack(words: np.ndarray, width: int, ilv: int = 1) -> np.ndarray:
-    """(rows, pitch) int32 -> (rows, width) uint8 cells."""
-    bits = np.unpackbits(words.astype("<u4").view(np.uint8), axis=1, bitorder="little")[:, :width]
-    out = np.empty_like(bits)
-    out[:, _cell_of_bit(width, ilv)] = bits
-    return out
-
-
-def _pack(cells: np.ndarray, pitch: int, ilv: int = 1) -> np.ndarray:
-    rows, width = cells.shape
-    padded = np.zeros((rows, pitch * 32), np.uint8)
-    padded[:, :width] = cells[:, _cell_of_bit(width, ilv)]
-    return np.packbits(padded, axis=1, bitorder="little").view("<u4").astype(np.uint32).view(np.int32)
+from strip_arena import pack as _pack, unpack as _unpack  # host-side pack / unpack of the strip layout
 
 
 class OracleEngine:
@@ -71,14 +49,17 @@ class OracleEngine:
         # the k-row light cone that is discarded below
         res = o.c_run(cells, k, geom.boundary)
         out = res[out_begin - lo:out_end - lo]
-        dst.numpy()[out_begin + g:out_end + g] = _pack(out, geom.pitch, geom.ilv)
+        words = geom.width // 32  # only the board's words: a caller's pad words are not the pass's to write
+        dst.numpy()[out_begin + g:out_end + g, :words] = _pack(out, words, geom.ilv)
 
     def seed_splitmix(self, geom, buf, seed, stream=None):
         full = o.seed_splitmix(geom.width, geom.height, seed)
-        buf.numpy()[geom.ghost:geom.ghost + geom.rows] = _pack(full[geom.y0:geom.y0 + geom.rows], geom.pitch, geom.ilv)
+        words = geom.width // 32
+        buf.numpy()[geom.ghost:geom.ghost + geom.rows, :words] = _pack(full[geom.y0:geom.y0 + geom.rows], words, geom.ilv)
 
     def set_cells(self, geom, buf, cells_u8, stream=None):
-        buf.numpy()[geom.ghost:geom.ghost + geom.rows] = _pack(np.asarray(cells_u8, np.uint8), geom.pitch, geom.ilv)
+        words = geom.width // 32
+        buf.numpy()[geom.ghost:geom.ghost + geom.rows, :words] = _pack(np.asarray(cells_u8, np.uint8), words, geom.ilv)
 
     def get_cells(self, geom, buf, stream=None):
         return torch.from_numpy(_unpack(buf.numpy()[geom.ghost:geom.ghost + geom.rows], geom.width, geom.ilv))

@@ -318,6 +318,25 @@ def test_strip_validation_without_gpu():
     # a k-generation pass needs k ghost rows when rows do not wrap
     dummy = ctypes.c_void_p(16)
     assert lib.gol_strip_step(ctypes.byref(s), dummy, ctypes.c_void_p(32), 4, 0, 10, None) == _lib.GOL_ERR_INVALID
+    # the pitch: at least the row and a multiple of ilv, nothing more (a pad of one block is legal, and so is one that
+    # leaves rows off a 16-byte boundary at ilv 1 / 2)
+    for ilv in (1, 2, 4):
+        words = 64 * ilv
+        pitches = [(words, True), (words + ilv, True), (words + 3 * ilv, True), (words - ilv, False)]
+        if ilv > 1:
+            pitches.append((words + 1, False))
+        for pitch, ok in pitches:
+            p = _lib.Strip(32 * words, 50, 0, 50, 0, pitch, 0, 1, ilv, 0)
+            rc = lib.gol_strip_plan(ctypes.byref(p), 4, 0, 50, None, None)
+            assert rc == (_lib.GOL_OK if ok else _lib.GOL_ERR_INVALID), (ilv, pitch)
+        # the step moves a lane's block as one 4 * ilv-byte access: src and dst on that boundary, refused before any
+        # device work otherwise (gol.h, gol_strip_step)
+        p = _lib.Strip(32 * words, 50, 0, 50, 0, words + ilv, 0, 1, ilv, 0)
+        for src, dst in ((4096 + 4 * ilv - 4, 8192), (4096, 8192 + 4 * ilv - 4), (4096 + 8, 8192)):
+            if src % (4 * ilv) == 0 and dst % (4 * ilv) == 0:
+                continue  # ilv 1: every word pointer is aligned
+            rc = lib.gol_strip_step(ctypes.byref(p), ctypes.c_void_p(src), ctypes.c_void_p(dst), 4, 0, 50, None)
+            assert rc == _lib.GOL_ERR_INVALID and b"aligned" in lib.gol_last_error(), (ilv, src, dst)
 
 
 # ---------------------------------------------------------------- mirror of the F# types

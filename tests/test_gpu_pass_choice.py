@@ -65,6 +65,56 @@ def test_pass_choice(gol, oracle, w, h, boundary, options, kw, gens, want):
         assert b.get_option("last_pass") == want  # the readback changes nothing
 
 
+def _canonical_words(cells):
+    """The snapshot layout of gol_save_packed / gol_load_packed: row y is ceil(w / 64) uint64, bit i of word j = cell
+    (64 j + i, y)."""
+    h, w = cells.shape
+    nc = (w + 63) // 64
+    padded = np.zeros((h, nc * 64), np.uint8)
+    padded[:, :w] = cells
+    return np.packbits(padded, axis=1, bitorder="little").view("<u8").reshape(h * nc)
+
+
+SETTERS = ("set_cells", "load_packed", "seed_splitmix")
+
+
+# the table's shapes; the 8224-wide board with 512 rows (its width picks the pass, asserted below; 4096 rows take 13 s)
+DIRTY = [(w, 512 if w * h > 2**24 else h, *rest) for w, h, *rest in CASES]
+
+
+@pytest.mark.parametrize("case", range(len(CASES)), ids=lambda i: f"{DIRTY[i][0]}x{DIRTY[i][1]}-pass{DIRTY[i][6]}-{SETTERS[i % 3]}")
+def test_pass_choice_on_a_dirtied_handle(gol, oracle, case):
+    """A board handle's buffers cannot be poisoned from outside, so they are dirtied from inside: every pass of the
+    table first runs an all-ones board and then noise for the case's generations -- which leaves the ping-pong buffer,
+    the ragged scratch rows, the ring copies and the hand-off granules holding another board -- before the board is
+    overwritten (set_cells, load_packed or seed_splitmix, one per case) and stepped.  The result must be the oracle's
+    and a fresh handle's: nothing of the earlier boards may reach it."""
+    w, h, boundary, options, kw, gens, want = DIRTY[case]
+    setter = SETTERS[case % 3]
+    b0 = oracle.seed_splitmix(w, h, 77 + case) if setter == "seed_splitmix" else _rand(h, w, 5000 + case)
+    with gol.Board(w, h, boundary, options=options, **kw) as fresh:
+        fresh.set_cells(b0).step(gens)
+        assert fresh.get_option("last_pass") == want
+        fresh_hash, fresh_pop = fresh.hash(), fresh.population()
+    with gol.Board(w, h, boundary, options=options, **kw) as b:
+        b.set_cells(np.ones((h, w), np.uint8)).step(gens)
+        assert b.get_option("last_pass") == want
+        b.set_cells(_rand(h, w, 6000 + case, 0.5)).step(gens)
+        assert b.get_option("last_pass") == want and b.generation == gens
+        if setter == "set_cells":
+            b.set_cells(b0)
+        elif setter == "load_packed":
+            b.load_packed(_canonical_words(b0))
+        else:
+            b.seed_splitmix(77 + case)
+        assert b.generation == 0
+        b.step(gens)
+        assert b.get_option("last_pass") == want
+        assert (b.hash(), b.population()) == (fresh_hash, fresh_pop)
+        np.testing.assert_array_equal(b.get_cells(), oracle.c_run(b0, gens, boundary))
+        assert b.generation == gens
+
+
 def test_pass_choice_follows_the_call_length_on_a_ragged_board(gol, oracle):
     """The chooser meeting the ragged state: a long call leaves the board in the streaming pass's scratch rows, a short
     one brings the bytes up to date and steps them, the next long one packs them again."""
