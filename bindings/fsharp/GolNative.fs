@@ -95,6 +95,10 @@ extern int gol_batch_hashes(nativeint batch, uint64[] hashes, int64 n)
 extern int gol_batch_render_gray8(nativeint batch, int64 board, byte[] pixels, int64 stride, byte aliveValue)
 [<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
 extern int gol_batch_synchronize(nativeint batch)
+// the ensemble's cycle census (gol.h): transient, period and population of every board's cycle within maxGenerations;
+// steps may be null
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int gol_ensemble_cycles(nativeint batch, int64 maxGenerations, int64[] transient, int64[] period, int64[] population, int64[] steps, int64 n)
 [<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
 extern nativeint gol_last_error()
 

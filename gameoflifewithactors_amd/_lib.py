@@ -173,8 +173,10 @@ SIGNATURES = {
     "gol_batch_hashes": (ctypes.c_int, [vp, u64p, i64]),
     "gol_batch_render_gray8": (ctypes.c_int, [vp, i64, u8p, i64, ctypes.c_uint8]),
     "gol_batch_synchronize": (ctypes.c_int, [vp]),
+    "gol_ensemble_cycles": (ctypes.c_int, [vp, i64, i64p, i64p, i64p, i64p, i64]),
     # test and A/B knobs (csrc/gol_debug.h: internal, not part of the gol.h boundary)
     "gol_debug_batch_group_waves": (ctypes.c_int, [vp, ctypes.c_int]),
+    "gol_debug_ensemble_cycles_us": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_double)]),
     "gol_debug_set_option": (ctypes.c_int, [vp, ctypes.c_char_p, i64]),
     "gol_debug_get_option": (ctypes.c_int, [vp, ctypes.c_char_p, i64p]),
     "gol_debug_option_names": (ctypes.c_char_p, []),

@@ -5,7 +5,11 @@ Reference seam: the reference's board is 100 x 100 and seeded from ``DateTime.No
 One ``BoardBatch`` holds ``count`` such boards bit-packed in HBM and ``step(g)`` advances all of them ``g`` generations
 in ONE launch, one wavefront per board (``csrc/gol_batch.hip``) -- where a ``Board`` per seed would
 step them one single-wave launch after another.  ``step_trace`` samples every board's population inside that launch:
-population curves, extinction times and soup censuses over thousands of seeds are one call.
+population curves, extinction times and soup censuses over thousands of seeds are one call.  ``cycles`` answers the
+other question asked of an ensemble of soups -- after how many generations does each board settle, and into a cycle of
+what period -- in one launch too: each wave runs the cycle search on the board in its registers
+(``csrc/gol_cycles.hip``), where ``step(1)`` + ``hashes()`` per generation would be thousands of launches
+and readbacks.
 """
 from __future__ import annotations
 
@@ -146,6 +150,27 @@ class BoardBatch:
         out = np.empty(self.count, dtype=np.uint64)
         check(self._lib.gol_batch_hashes(self._h, out.ctypes.data_as(_lib.u64p), out.size), "gol_batch_hashes")
         return out
+
+    def cycles(self, max_generations: int, with_steps: bool = False):
+        """The cycle every board's current cells run into, searched for ``max_generations`` generations at most
+        (1 .. 2**20): ``(transient, period, population)``, each a (count,) int64 array, and ``steps`` as a fourth when
+        ``with_steps``.
+
+        For board i let B_0 be its current cells and B_{t+1} the next B3/S23 generation of B_t under the batch's
+        boundary, t* the smallest t >= 1 with B_t == B_s for some s < t, mu = s (the transient) and lambda = t* - mu
+        (the period, minimal by construction).  Resolved, exactly when t* = mu + lambda <= max_generations:
+        ``transient[i] = mu``, ``period[i] = lambda``, ``population[i]`` = live cells of B_mu.  Unresolved, exactly when
+        t* > max_generations: ``(-1, 0, 0)``.  The answer depends on the board and ``max_generations`` only, never on
+        how the search went.  Cells are compared in place: a glider on a 100 x 100 torus is ``(0, 400, 5)``, a still
+        life ``(0, 1, population)``, an empty board ``(0, 1, 0)``.
+
+        Read-only: cells, hashes and ``generation`` are unchanged.  ``steps[i]`` is the number of generation steps the
+        wave ran for board i -- cost accounting, not a property of the board, free to change between versions, never
+        above ``6 * max_generations`` (the worst case: an unresolved board)."""
+        out = [np.empty(self.count, dtype=np.int64) for _ in range(4 if with_steps else 3)]
+        ptrs = [a.ctypes.data_as(_lib.i64p) for a in out] + ([] if with_steps else [None])
+        check(self._lib.gol_ensemble_cycles(self._h, max_generations, *ptrs, self.count), "gol_ensemble_cycles")
+        return tuple(out)
 
     def info(self) -> dict:
         w, h, c = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()

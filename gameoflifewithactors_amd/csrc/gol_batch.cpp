@@ -9,6 +9,7 @@
 
 #include "gol_batch_host.h"
 #include "gol_board.h"
+#include "gol_cycle_search.h"
 #include "gol_debug.h"
 
 using gol::DeviceBuffer;
@@ -24,7 +25,9 @@ struct gol_batch {
     int nw = 0;            // words per row
     int group_waves = 1;   // boards per workgroup (gol_debug_batch_group_waves; DESIGN.md 4.9 has the A/B)
     uint32_t* words = nullptr;  // count * H * nw
+    int32_t* cycles = nullptr;  // count * 4 result words of gol_ensemble_cycles, allocated by its first call
     int64_t generation = 0;
+    double cycles_us = -1;  // device time of the last census launch (gol_debug_ensemble_cycles_us)
 
     int64_t cells() const { return W * H; }
     int64_t board_words() const { return H * nw; }
@@ -47,6 +50,7 @@ int with_batch(gol_batch* b, F&& f) {
 
 void free_batch(gol_batch* b) {
     if (b->words) (void)hipFree(b->words);
+    if (b->cycles) (void)hipFree(b->cycles);
     if (b->stream) (void)hipStreamDestroy(b->stream);
     delete b;
 }
@@ -302,6 +306,43 @@ int gol_batch_render_gray8(gol_batch* b, int64_t board, uint8_t* pixels, int64_t
     });
 }
 
+int gol_ensemble_cycles(gol_batch* b, int64_t max_generations, int64_t* transient, int64_t* period,
+                        int64_t* population, int64_t* steps, int64_t n) {
+    return with_batch(b, [&] {
+        if (!transient || !period || !population || n != b->count)
+            return fail(GOL_ERR_INVALID, "transient, period and population must hold count entries");
+        if (max_generations < 1 || max_generations > gol::kCycleGenerationsMax)
+            return fail(GOL_ERR_INVALID, "max_generations must be 1..2^20");
+        static_assert(gol::kBatchCountMax * 4 * (int64_t)sizeof(int32_t) <= kStagingBytes, "one copy of the results");
+        const size_t bytes = (size_t)b->count * 4 * sizeof(int32_t);
+        if (!b->cycles) {
+            const hipError_t e = hipMalloc(reinterpret_cast<void**>(&b->cycles), bytes);
+            if (e != hipSuccess) {
+                b->cycles = nullptr;
+                return fail(GOL_ERR_OOM, std::string("hipMalloc cycle results: ") + hipGetErrorString(e));
+            }
+        }
+        std::vector<int32_t> host((size_t)b->count * 4);
+        gol::EventPair ev;
+        GOL_RC(ev.create());
+        GOL_HIP(hipEventRecord(ev.e0, b->stream));
+        GOL_HIP(gol::launch_batch_cycles(b->words, b->count, b->W, b->H, b->boundary == GOL_BOUNDED, max_generations,
+                                         b->cycles, b->stream));
+        GOL_HIP(hipEventRecord(ev.e1, b->stream));
+        GOL_HIP(hipMemcpyAsync(host.data(), b->cycles, bytes, hipMemcpyDeviceToHost, b->stream));
+        GOL_HIP(hipStreamSynchronize(b->stream));
+        GOL_RC(ev.elapsed_us(&b->cycles_us));
+        for (int64_t i = 0; i < n; i++) {  // the caller's arrays are written only once every device call succeeded
+            const int32_t* r = host.data() + 4 * i;
+            transient[i] = r[0];
+            period[i] = r[1];
+            population[i] = r[2];
+            if (steps) steps[i] = r[3];
+        }
+        return GOL_OK;
+    });
+}
+
 int gol_batch_synchronize(gol_batch* b) {
     return with_batch(b, [&] {
         GOL_HIP(hipStreamSynchronize(b->stream));
@@ -313,6 +354,15 @@ int gol_debug_batch_group_waves(gol_batch* b, int waves) {
     return with_batch(b, [&] {
         if (waves != 1 && waves != 4) return fail(GOL_ERR_INVALID, "waves per workgroup must be 1 or 4");
         b->group_waves = waves;
+        return GOL_OK;
+    });
+}
+
+int gol_debug_ensemble_cycles_us(gol_batch* b, double* elapsed_us) {
+    return with_batch(b, [&] {
+        if (!elapsed_us) return fail(GOL_ERR_INVALID, "null elapsed_us");
+        if (b->cycles_us < 0) return fail(GOL_ERR_INVALID, "no gol_ensemble_cycles call on this batch yet");
+        *elapsed_us = b->cycles_us;
         return GOL_OK;
     });
 }

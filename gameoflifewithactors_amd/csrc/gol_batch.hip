@@ -17,22 +17,6 @@
 namespace gol {
 namespace {
 
-// Sum of v over the wave's 64 lanes, the same value in every lane: four DPP adds leave every lane of a row of 16 with
-// the row's sum (quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror, row_mirror), then the four rows' sums are
-// read as scalars.  Every lane of the wave must be executing.
-template <int CTRL>
-__device__ __forceinline__ uint32_t dpp_read(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, true);
-}
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-    v += dpp_read<0xB1>(v);
-    v += dpp_read<0x4E>(v);
-    v += dpp_read<0x141>(v);
-    v += dpp_read<0x140>(v);
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, 0) + (uint32_t)__builtin_amdgcn_readlane((int)v, 16) +
-           (uint32_t)__builtin_amdgcn_readlane((int)v, 32) + (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
-}
-
 // Board `blockIdx.x * waves per group + wave` runs `samples` x `every` generations.  TRACE: after each `every`
 // generations the board's population goes to trace[t * count + board] (t = 0 .. samples - 1); otherwise samples is 1
 // and trace unused.  A wave past the last board leaves before it touches memory.

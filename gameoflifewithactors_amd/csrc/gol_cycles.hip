@@ -1,0 +1,130 @@
+// gol_cycles.hip -- the ensemble cycle census (gol_ensemble_cycles): for every board of a batch, after
+// how many generations it enters a cycle and of what period, one wavefront per board, in one launch (gfx950).
+//
+// A wave loads its board into registers as the batch step does (gol_batch.hip: same layout, same geometry, lane L holds
+// rows L*RPL ..), and runs the search of gol_cycle_search.h on it: the generation is wave_generation (gol_wave_body.h),
+// two boards are compared in registers, and nothing is stored but the board's four result words.  The boards are const.
+//
+// Every lane of the wave runs every generation (the row exchange reads its neighbours' registers), so every branch of
+// the search must be wave-uniform: `equal` reduces the lanes' differences with one ballot, whose result is a scalar,
+// and the search's counters depend on nothing else.
+#include "gol_batch_host.h"
+#include "gol_cycle_search.h"
+#include "gol_internal.h"
+#include "gol_wave_body.h"
+
+namespace gol {
+namespace {
+
+struct CycleWave {
+    WaveGeom geom;
+    uint64_t lanes;  // the lanes that hold rows of the board: what the others hold never counts as a difference
+};
+
+// One board in the wave's registers, as the search's state type.
+template <int NW, int RPL, bool BOUNDED>
+struct WaveBoard {
+    uint32_t w[RPL][NW];
+    const CycleWave* wave;
+
+    __device__ __forceinline__ void step() { wave_generation<NW, RPL, BOUNDED>(w, wave->geom); }
+    // the same value in every lane: each lane ORs the XOR of its words (one v_bitop3 per word), one ballot
+    __device__ __forceinline__ bool equal(const WaveBoard& o) const {
+        uint32_t d = 0;
+#pragma unroll
+        for (int i = 0; i < RPL; i++)
+#pragma unroll
+            for (int j = 0; j < NW; j++) d = lut3<0xBE>(d, w[i][j], o.w[i][j]);  // d | (a ^ b)
+        return (__ballot(d != 0) & wave->lanes) == 0;
+    }
+};
+
+// Board blockIdx.x: out[4 board ..] = transient, period, population of B_transient, generation steps run.
+template <int NW, int RPL, bool BOUNDED>
+__global__ __launch_bounds__(64) void gol_batch_cycles(const uint32_t* __restrict__ words, int64_t count, int W, int H,
+                                                       int max_generations, int32_t* __restrict__ out) {
+    const int lane = threadIdx.x;
+    const int64_t board = blockIdx.x;
+    if (board >= count) return;
+    const int nl = H / RPL;  // active lanes
+    const bool active = lane < nl;
+    const uint32_t* rows = words + (board * H + lane * RPL) * NW;  // this lane's RPL * NW words
+    CycleWave cw;
+    cw.geom = wave_geom<BOUNDED>(W, nl, lane);
+    cw.lanes = __ballot(active);
+    using Board = WaveBoard<NW, RPL, BOUNDED>;
+    const auto load = [&]() {
+        Board b;
+        b.wave = &cw;
+#pragma unroll
+        for (int i = 0; i < RPL; i++)
+#pragma unroll
+            for (int j = 0; j < NW; j++) b.w[i][j] = 0;
+        if (active) {  // (an inactive lane's `rows` points past its board: never dereferenced)
+#pragma unroll
+            for (int i = 0; i < RPL; i++)
+#pragma unroll
+                for (int j = 0; j < NW; j++) b.w[i][j] = rows[i * NW + j];
+        }
+        return b;
+    };
+    uint32_t pop = 0;
+    const CycleResult r = cycle_search<Board>(load, max_generations, [&](const Board& a) {
+        uint32_t n = 0;
+#pragma unroll
+        for (int i = 0; i < RPL; i++)
+#pragma unroll
+            for (int j = 0; j < NW; j++) n += __popc(a.w[i][j]);
+        pop = wave_sum_u32(active ? n : 0u);
+    });
+    if (lane == 0) {
+        int32_t* o = out + 4 * board;
+        o[0] = r.transient;
+        o[1] = r.period;
+        o[2] = (int32_t)pop;
+        o[3] = r.steps;
+    }
+}
+
+template <int NW, int RPL>
+hipError_t cycles_nr(const uint32_t* words, int64_t count, int W, int H, bool bounded, int G, int32_t* out,
+                     hipStream_t s) {
+    const dim3 grid((unsigned)count), block(64);  // count <= 2^22
+    if (bounded)
+        hipLaunchKernelGGL((gol_batch_cycles<NW, RPL, true>), grid, block, 0, s, words, count, W, H, G, out);
+    else
+        hipLaunchKernelGGL((gol_batch_cycles<NW, RPL, false>), grid, block, 0, s, words, count, W, H, G, out);
+    return hipGetLastError();
+}
+
+template <int NW>
+hipError_t cycles_n(const uint32_t* words, int64_t count, int W, int H, bool bounded, int G, int32_t* out, int rpl,
+                    hipStream_t s) {
+    switch (rpl) {
+        case 1: return cycles_nr<NW, 1>(words, count, W, H, bounded, G, out, s);
+        case 2: return cycles_nr<NW, 2>(words, count, W, H, bounded, G, out, s);
+        case 3: return cycles_nr<NW, 3>(words, count, W, H, bounded, G, out, s);
+        case 4: return cycles_nr<NW, 4>(words, count, W, H, bounded, G, out, s);
+    }
+    return hipErrorInvalidValue;
+}
+
+}  // namespace
+
+hipError_t launch_batch_cycles(const uint32_t* words, int64_t count, int64_t W, int64_t H, bool bounded,
+                               int64_t max_generations, int32_t* out, hipStream_t s) {
+    const int rpl = wave_resident_rpl(W, H);
+    if (!rpl || !words || !out || count < 1 || count > kBatchCountMax || max_generations < 1 ||
+        max_generations > kCycleGenerationsMax)
+        return hipErrorInvalidValue;
+    const int G = (int)max_generations;
+    switch ((int)((W + 31) / 32)) {
+        case 1: return cycles_n<1>(words, count, (int)W, (int)H, bounded, G, out, rpl, s);
+        case 2: return cycles_n<2>(words, count, (int)W, (int)H, bounded, G, out, rpl, s);
+        case 3: return cycles_n<3>(words, count, (int)W, (int)H, bounded, G, out, rpl, s);
+        case 4: return cycles_n<4>(words, count, (int)W, (int)H, bounded, G, out, rpl, s);
+    }
+    return hipErrorInvalidValue;
+}
+
+}  // namespace gol

@@ -256,4 +256,10 @@ hipError_t launch_batch_unpack(const uint32_t* words, uint8_t* out, int64_t W, i
 // board i <- the cells gol_seed_splitmix(seed + i) gives a single W x H board
 hipError_t launch_batch_splitmix(uint32_t* words, int64_t count, int64_t W, int64_t H, uint64_t seed, hipStream_t s);
 
+// ---- gol_cycles.hip: the cycle census of a batch (gol_cycle_search.h), one wave per board, boards read only.
+// out[4 i ..] = transient (-1 unresolved), period, population of B_transient, generation steps run, for
+// 1 <= max_generations <= 2^20
+hipError_t launch_batch_cycles(const uint32_t* words, int64_t count, int64_t W, int64_t H, bool bounded,
+                               int64_t max_generations, int32_t* out, hipStream_t s);
+
 }  // namespace gol

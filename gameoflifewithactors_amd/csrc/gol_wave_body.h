@@ -1,5 +1,6 @@
 // gol_wave_body.h -- one generation of a board held in one wavefront's registers: the arithmetic the single-wave
-// pass (gol_wave.hip) and the batch pass (gol_batch.hip, one wave per board) share.
+// pass (gol_wave.hip), the batch pass (gol_batch.hip, one wave per board) and the cycle census (gol_cycles.hip) share,
+// and the wave-wide sum the batch's population trace and the census use.
 //
 //   lane L holds rows L*RPL .. L*RPL + RPL-1 (RPL = rows per lane, H % RPL == 0, nl = H / RPL <= 64 active lanes),
 //   each as NW = ceil(W / 32) words, bit b of word j = cell 32 j + b, bits >= W zero.
@@ -90,6 +91,22 @@ __device__ __forceinline__ void wave_generation(uint32_t (&w)[RPL][NW], const Wa
             if (j == NW - 1) v &= g.lastmask;
             w[i][j] = v;
         }
+}
+
+// Sum of v over the wave's 64 lanes, the same value in every lane: four DPP adds leave every lane of a row of 16 with
+// the row's sum (quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror, row_mirror), then the four rows' sums are
+// read as scalars.  Every lane of the wave must be executing.
+template <int CTRL>
+__device__ __forceinline__ uint32_t dpp_read(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, true);
+}
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
+    v += dpp_read<0xB1>(v);
+    v += dpp_read<0x4E>(v);
+    v += dpp_read<0x141>(v);
+    v += dpp_read<0x140>(v);
+    return (uint32_t)__builtin_amdgcn_readlane((int)v, 0) + (uint32_t)__builtin_amdgcn_readlane((int)v, 16) +
+           (uint32_t)__builtin_amdgcn_readlane((int)v, 32) + (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
 }
 
 }  // namespace gol

@@ -291,6 +291,23 @@ int gol_batch_hashes(gol_batch* b, uint64_t* out, int64_t n);
 /* One board's frame, as gol_render_gray8: pixels[x + y*stride] = alive ? alive_value : 0, stride >= width. */
 int gol_batch_render_gray8(gol_batch* b, int64_t board, uint8_t* pixels, int64_t stride, uint8_t alive_value);
 int gol_batch_synchronize(gol_batch* b);
+/* The ensemble's cycle census: for every board, after how many generations it enters a cycle and of
+ * what period, one launch, one wavefront per board, the search in that wave's registers.
+ *   Definition: B_0 = board i's current cells, B_(t+1) = the next B3/S23 generation of B_t under the batch's boundary;
+ *     t* = the smallest t >= 1 with B_t = B_s for some s < t; transient mu = s, period lambda = t* - mu (minimal).
+ *     Resolved, exactly when t* = mu + lambda <= max_generations: transient[i] = mu, period[i] = lambda, population[i] =
+ *     live cells of B_mu.  Unresolved, exactly when t* > max_generations: transient[i] = -1, period[i] = 0,
+ *     population[i] = 0.  The answer is a property of the board and max_generations, not of the search.  Cells are
+ *     compared in place: a glider on a torus has the period of its return, not 4.
+ *   Arguments: n == count; 1 <= max_generations <= 2^20; transient, period and population hold n entries; steps may be
+ *     NULL.  Anything else returns GOL_ERR_INVALID before any device work and leaves the arrays untouched.
+ *   steps[i] = generation steps the wave ran for board i: cost accounting, not a property of the board, and free to
+ *     change between versions; never more than 6 * max_generations.  That is the worst case, an unresolved board, and
+ *     what the cap of 2^20 bounds: a launch ends when its slowest board does (DESIGN.md 4.9 has the time of a step).
+ * Read-only: the boards, the generation counter and the hashes are unchanged.  Synchronous (the results are host
+ * arrays).  Not named gol_batch_*: it answers a question about the ensemble, and takes the batch as its argument. */
+int gol_ensemble_cycles(gol_batch* b, int64_t max_generations, int64_t* transient, int64_t* period,
+                        int64_t* population, int64_t* steps, int64_t n);
 
 const char* gol_last_error(void);
 const char* gol_version(void);

@@ -141,6 +141,19 @@ class Batch {
         return p;
     }
     void synchronize() { check(gol_batch_synchronize(b_), "gol_batch_synchronize"); }
+    // gol_ensemble_cycles: per board the transient, period and population of the cycle its current cells run into
+    // within max_generations generations, (-1, 0, 0) where they do not; `steps` is the cost accounting gol.h describes
+    struct Cycles {
+        std::vector<int64_t> transient, period, population, steps;
+    };
+    Cycles cycles(int64_t max_generations) const {
+        Cycles c;
+        for (auto* v : {&c.transient, &c.period, &c.population, &c.steps}) v->resize((size_t)n_);
+        check(gol_ensemble_cycles(b_, max_generations, c.transient.data(), c.period.data(), c.population.data(),
+                                  c.steps.data(), n_),
+              "gol_ensemble_cycles");
+        return c;
+    }
 
    private:
     gol_batch* b_ = nullptr;
