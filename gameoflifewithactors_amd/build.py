@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libgol_hip.so")
-SOURCES = [os.path.join(CSRC, f) for f in ("gol_step.hip", "gol_formats.hip", "gol_resident.hip", "gol_wave.hip", "gol_coop.hip", "gol_lanes.hip", "gol_pipe.hip", "gol_view.hip", "gol_batch.hip", "gol_cycles.hip", "gol_capi.cpp", "gol_passes.cpp", "gol_policy.cpp", "gol_strip.cpp", "gol_options.cpp", "gol_multi.cpp", "gol_batch.cpp")]
+SOURCES = [os.path.join(CSRC, f) for f in ("gol_step.hip", "gol_formats.hip", "gol_resident.hip", "gol_wave.hip", "gol_coop.hip", "gol_lanes.hip", "gol_pipe.hip", "gol_view.hip", "gol_batch.hip", "gol_cycles.hip", "gol_stream_plan.cpp", "gol_capi.cpp", "gol_passes.cpp", "gol_policy.cpp", "gol_strip.cpp", "gol_options.cpp", "gol_multi.cpp", "gol_batch.cpp")]
 HEADERS = [
     os.path.join(CSRC, "gol_bitlogic.h"),
     os.path.join(CSRC, "gol_layout.h"),
@@ -47,7 +47,7 @@ def _stale(target: str, deps: list[str]) -> bool:
 
 def build(force: bool = False, verbose: bool = True, lib: str = LIB, defines: tuple = (),
           step_src: str | None = None, flags: tuple = (), alt: dict | None = None) -> str:
-    """Compile SOURCES for gfx950 into `lib`.  `defines` (e.g. ("GOL_XLANE=0",)), `step_src` (another revision
+    """Compile SOURCES for gfx950 into `lib`.  `defines` (e.g. ("GOL_STAMP=1",)), `step_src` (another revision
     of gol_step.hip) and `alt` ({basename: path} of other revisions of any source) build A/B variants for
     experiments."""
     sources = [step_src or SOURCES[0]] + SOURCES[1:]

@@ -74,20 +74,24 @@ struct PipeArgs {
     int32_t live_lo, live_hi;
 };
 
-// ---- gol_step.hip
+// ---- gol_step.hip: the streaming pass's kernels, their variant table and the launch
 bool stream_supported(int k, int ilv);
+// rag_bits: cells in the last word of a ragged row (words = ceil(W / 32), ilv 1), 0 for whole-word rows
+int stream_wpb(int64_t words, int k, int ilv, bool bounded, bool wrap, int rag_bits = 0);  // waves per workgroup
+// waves of the pass's kernel the current device holds at once (4096 when no device answers)
+int64_t resident_units(int64_t words, int k, int ilv, bool bounded, bool wrap, int rag_bits);
+hipError_t launch_stream_step(const uint32_t* src, uint32_t* dst, StreamArgs a, int k, bool bounded, bool wrap,
+                              hipStream_t s);
+
+// ---- gol_stream_plan.cpp: the streaming pass's host planner
 int stream_max_k(int ilv);
 // the deepest supported depth <= cap and <= n for rows of `words` words (words 0: never a level-pipelined depth)
 int stream_largest_k(int64_t n, int cap, int ilv, int64_t words = 0, bool bounded = false);
-// rag_bits: cells in the last word of a ragged row (words = ceil(W / 32), ilv 1), 0 for whole-word rows
 int64_t stream_strips(int64_t words, int ilv, int k, bool bounded, int rag_bits = 0);
 int stream_pair_split(int k, int ilv, bool bounded, bool wrap, bool single);
 int stream_split2(int k, int ilv, bool bounded, bool wrap, bool single);
-int stream_wpb(int64_t words, int k, int ilv, bool bounded, bool wrap, int rag_bits = 0);
 // fills nstrips / nsegs / seg (one balanced round of resident waves unless a.seg_opt -- the "seg_rows" option -- is set)
 void plan_stream(StreamArgs& a, int k, bool bounded, bool wrap);
-hipError_t launch_stream_step(const uint32_t* src, uint32_t* dst, StreamArgs a, int k, bool bounded, bool wrap,
-                              hipStream_t s);
 // PipeArgs of a pass over StreamArgs' buffer (split options, error word, spare waves, the live rows of a bounded board)
 PipeArgs pipe_args(const StreamArgs& a, bool bounded);
 

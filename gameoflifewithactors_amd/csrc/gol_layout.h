@@ -20,6 +20,19 @@
 
 namespace gol {
 
+// Wave strips of the streaming pass, shared by its kernel (gol_step.hip) and its planner (gol_stream_plan.cpp): a
+// wavefront's 64 lanes hold one block each.
+static constexpr int kWave = 64;
+static constexpr int kInterior = kWave - 2;      // blocks stored per wave column strip (deep passes)
+static constexpr int kSeamInterior = kWave - 1;  // ... per seam strip (torus: one lane holds both halos)
+static constexpr int kDeepTripRows = 4;          // rows per loop trip of the deep passes (K > 1; gol_step.hip TripRows)
+// 8 waves per workgroup: the deep passes run 2-3 waves per SIMD, so a workgroup spans the CU's SIMDs
+// twice (profiles/r1/ab_fence2.log: +3-6 % at K = 16 / 32 over 4-wave workgroups)
+#ifndef GOL_WAVES_PER_BLOCK
+#define GOL_WAVES_PER_BLOCK 8
+#endif
+static constexpr int kWavesPerBlock = GOL_WAVES_PER_BLOCK;
+
 GOL_LAYOUT_HD int ilv_shift(int ilv) { return ilv == 4 ? 2 : (ilv == 2 ? 1 : 0); }
 
 // cell x of a row -> (stored word index within the row, bit)

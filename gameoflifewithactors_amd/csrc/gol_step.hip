@@ -19,7 +19,24 @@
 // moves in one or both directions (ab_xlane2.log, variant_job_ab.log), batched / late exchanges
 // (ab_early.log), breadth-first levels (ab_breadth.log), per-row-pair fences (ab_fence.log), s_setprio
 // fairness (tail_*.log), 8-row trips (ab_r8.log) and the no-memory / no-arithmetic ceiling builds
-// (ceiling_ab.log).
+// (ceiling_ab.log).  From the seam strips' rounds (DESIGN.md 4.1 "Seam strips"; built by macros this file no longer
+// has):
+//   - zero-fill shifts on the torus, and no seam load or merge (timing studies, wrong boards: they priced the
+//     rotates and the seam against the bounded pass): profiles/r5/torus_pieces_k.jsonl
+//   - the torus compiled without seam strips (halo-lane strips of 62): profiles/r5/torus_noseam_v.jsonl
+//   - round 3's per-row seam DMAs (M more DMAs per row; SQ_INSTS_VMEM_RD / SQ_INSTS_LDS 1.93x the bounded pass's):
+//     profiles/r3/pmc_sq, profiles/r4/ab_seam1_torus.log
+//   - round 4's one seam DMA per trip into a 64-dword LDS slot, read back as a broadcast: 434.6 us per (12, 2) pass
+//     against 431.8 for the scalar loads: profiles/r5/torus_seam_smem_y.jsonl
+//   - each row's seam s_load issued with the row's DMAs: its fills missed L2 (HBM fetch +13 %), 440.3 us against
+//     431.8 for the loads at the previous trip's end: profiles/r5/torus_seam_late_z.jsonl, fetch_seam_smem*_z.json
+//   - one dwordx3 DMA per row at M = 2: 12-byte lane stride in the stage, spilled the (12, 2) pass (no log kept)
+//   - prefetch placements other than StreamWave's (modes 0 / 1 / 3 / 5, see the trip's hook):
+//     profiles/r3/ab_spread_modes_i.log, profiles/r4/ab_spread_o.log, ab_spread5_q.log
+//   - the bounded deep passes spreading their row DMAs over the levels: -5 %, profiles/r3/ab_spread_h.log,
+//     profiles/r5/bounded_spread_t.jsonl
+//   - a running row address (reset at the wrap) on the single-board torus: -8 % on (12, 2),
+//     profiles/r3/ab_torus_load_addr.log ("new" vs "wl"), profiles/r5/torus_wrapptr_q.jsonl
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -36,15 +53,7 @@ extern "C" unsigned gol_debug_bounds_formats(void);  // gol_formats.hip
 #endif
 namespace gol {
 
-static constexpr int kWave = 64;
-static constexpr int kInterior = kWave - 2;  // blocks stored per wave column strip (deep passes)
-static constexpr int kSeamInterior = kWave - 1;  // ... per seam strip (torus: one lane holds both halos)
-// 8 waves per workgroup: the deep passes run 2-3 waves per SIMD, so a workgroup spans the CU's SIMDs
-// twice (profiles/r1/ab_fence2.log: +3-6 % at K = 16 / 32 over 4-wave workgroups)
-#ifndef GOL_WAVES_PER_BLOCK
-#define GOL_WAVES_PER_BLOCK 8
-#endif
-static constexpr int kWavesPerBlock = GOL_WAVES_PER_BLOCK;
+// (kWave, kInterior, kSeamInterior, kWavesPerBlock, kDeepTripRows: gol_layout.h, shared with the planner)
 // Waves per workgroup of a variant: 4 x the waves each SIMD holds at the kernel's register footprint, so
 // ONE workgroup fills a CU and the waves sharing a SIMD (w, w + 4, w + 8) belong to the same workgroup
 // (their age order is then known: see the group split in plan_stream).  (K, M) = (12, 2) runs 12-wave
@@ -64,60 +73,17 @@ struct Wpb {
 // ROT (torus): rotates, so lane 0's left neighbour is lane 63 -- the seam lane of a seam strip, a halo lane (whose
 // outer edge is garbage anyway) otherwise.  Bounded boards shift with zero fill: the dead cells beyond the
 // board's edge in the edge-fill strips.
-// GOL_AB_TORUS_SHIFT, GOL_AB_NOSEAMDMA (timing studies only, WRONG boards): the torus deep pass with the bounded
-// pass's zero-fill shifts instead of rotates / without its seam DMA and merge, to price each against the bounded pass
-#ifndef GOL_AB_TORUS_SHIFT
-#define GOL_AB_TORUS_SHIFT 0
-#endif
-#ifndef GOL_AB_NOSEAMDMA
-#define GOL_AB_NOSEAMDMA 0
-#endif
-// GOL_SEAM_SMEM (round 5, default 2): the seam lane's half-blocks read by the scalar unit -- the R x M seam words of a
-// trip are the same for every lane, so each row's M words come as one s_load into SGPRs -- instead of round 4's seam
-// LDS-DMA and its broadcast LDS reads at the trip's top.  1: each row's s_load with the row's DMAs; 2: the next trip's
-// R s_loads at the end of this trip, after its row DMAs have brought those lines (the seam block sits beside lane 0's)
-// into L2.  The (12, 2) torus pass drops from 164 to 156 VGPRs.  4 interleaved rounds at the bench window, us per
-// pass: 1 against the LDS seam 431.8 / 434.6 (profiles/r5/torus_seam_smem_y.jsonl), but its fills missed L2 (HBM fetch
-// +13 %); 2 against 1: 431.8 / 440.3 with the fetch bytes back at the LDS seam's (torus_seam_late_z.jsonl,
-// fetch_seam_smem*_z.json).  (The board buffer a pass reads is never written during it: the scalar cache, refilled
-// at every dispatch, holds no stale line.)
-#ifndef GOL_SEAM_SMEM
-#define GOL_SEAM_SMEM 2
-#endif
-// GOL_AB_BSPREAD (A/B): the bounded deep passes spread their row DMAs over the levels as the torus ones do
-#ifndef GOL_AB_BSPREAD
-#define GOL_AB_BSPREAD 0
-#endif
-// GOL_AB_WRAPPTR (A/B): the single-board torus walks its rows with a running address (reset at the wrap), as the
-// bounded pass does, instead of a 64-bit row multiply per row
-#ifndef GOL_AB_WRAPPTR
-#define GOL_AB_WRAPPTR 0
-#endif
 template <bool ROT>
 __device__ __forceinline__ uint32_t from_left(uint32_t v) {  // lane i <- lane i-1
-    if (ROT && !GOL_AB_TORUS_SHIFT) return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x13C, 0xf, 0xf, false);  // wave_ror:1
-    return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x138, 0xf, 0xf, true);              // wave_shr:1
+    if (ROT) return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x13C, 0xf, 0xf, false);  // wave_ror:1
+    return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x138, 0xf, 0xf, true);            // wave_shr:1
 }
 template <bool ROT>
 __device__ __forceinline__ uint32_t from_right(uint32_t v) {  // lane i <- lane i+1
-    if (ROT && !GOL_AB_TORUS_SHIFT) return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x134, 0xf, 0xf, false);  // wave_rol:1
-    return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x130, 0xf, 0xf, true);              // wave_shl:1
+    if (ROT) return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x134, 0xf, 0xf, false);  // wave_rol:1
+    return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x130, 0xf, 0xf, true);            // wave_shl:1
 }
 
-// Prefetch placement of the deep passes on seam strips (torus), GOL_SEAM_SPREAD: 0 = all R rows' DMAs at the trip's
-// top (the bounded passes' placement), 1 = one row's DMAs after each of the first R generation levels, 3 = the rows'
-// own-word DMAs at the top and one row's seam DMAs after each of the first R levels, 4 = row r's own-word DMAs after
-// level 2r and its seam DMAs after level 2r + 1, 5 = the same every 3 levels (3r, 3r + 1); -1 (default) = 4.  Rows a short pass (K below the
-// levels a mode needs) has not issued by its last level are issued after it; the pipeline-fill trips (which skip
-// levels) keep every DMA at the top.  Round 3, interleaved on one box at generation 300 (profiles/r3/ab_spread_modes_i.log),
-// GCUPS for modes 1 / 0 / 3 / 4: (12, 2) 114.3 / 113.4 / 113.6 / 113.8, (16, 2) 115.2 / 113.0 / 115.4 / 116.5.
-// On bounded boards (no seam DMAs) spreading lost 5 % (profiles/r3/ab_spread_h.log): they keep mode 0.
-// Round 4, one seam DMA per trip (GOL_SEAM1), (12, 2) at generation 300, 3 interleaved rounds (profiles/r4/
-// ab_spread_o.log), us per pass for modes 1 / 0 / 3 / 4: 440.8 / 508.1 / 503.7 / 435.9 -- (12, 2) moves to mode 4;
-// mode 5 against 4, 4 rounds on another box: 472.5 / 446.7 (ab_spread5_q.log).
-#ifndef GOL_SEAM_SPREAD
-#define GOL_SEAM_SPREAD -1
-#endif
 // GOL_STAMP (diagnostic builds only): every wave records its start / end time (s_memrealtime, 100 MHz)
 // into g_stamps; gol_debug_stamps() copies them out (tools/tail.py measures the launch tail)
 #ifndef GOL_STAMP
@@ -225,9 +191,8 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t checked_rsrc(const void* base,
 // flight for the memory-bound K = 1 pass, fewer for the deep passes whose registers hold the windows.
 template <int K, int M>
 struct TripRows {
-    static constexpr int value = (K == 1 && M == 1) ? 8 : 4;  // 8-row deep trips: -2.5 % (ab_r8.log)
+    static constexpr int value = (K == 1 && M == 1) ? 8 : kDeepTripRows;  // 8-row deep trips: -2.5 % (ab_r8.log)
 };
-
 // One wavefront's pipeline: K generation levels of 3-row windows of M-word blocks held in registers.
 // NARROW = 1 on a bounded board: the board is narrower than one wave strip, so lanes can lie off the board and every
 // level masks columns as well as rows.  Bounded boards at least a strip wide use edge-fill strips (no lane off
@@ -267,19 +232,7 @@ struct StreamWave {
     // break produces spread one cell per generation: after K <= 16M generations they have not reached either
     // end of the seam lane, so lanes 0..62 are exact.  One halo lane per wave instead of two: a 65536-cell row
     // at M = 2 is 16 seam strips plus 16 blocks, against 17 strips of 62 (DESIGN.md 4.1 "Seam strips").
-#ifndef GOL_AB_NOSEAM
-#define GOL_AB_NOSEAM 0
-#endif
-    static constexpr bool kSeam = !GOL_AB_NOSEAM && !BOUNDED && !(K == 1) && !kRagged;
-    // ONE seam DMA per trip (round 4): a global_load_lds_dword with a per-lane address, lane i loading word i % M of
-    // the block left of lane 0 in row (i / M) % R of the trip; the R x M words land side by side in a 64-dword LDS
-    // slot, which every lane then reads as a broadcast and only the seam lane merges (`hmask`).  Round 3 issued M
-    // DMAs per row (every lane reloading its own word, a cache hit, so that one lane in 64 got its half-block): twice
-    // the bounded pass's VMEM and LDS instructions (SQ_INSTS_VMEM_RD / SQ_INSTS_LDS 1.93x, profiles/r3/pmc_sq).
-#ifndef GOL_SEAM1
-#define GOL_SEAM1 1
-#endif
-    static constexpr bool kSeam1 = kSeam && GOL_SEAM1;
+    static constexpr bool kSeam = !BOUNDED && K != 1 && !kRagged;
     // Deep passes (K > 1) stage their prefetched rows through LDS (see `stage` below); the K = 1 pass keeps two
     // register buffers (it has registers to spare, and its halo-free strips load a neighbour word per row).
     static constexpr bool kStage = !kNoHalo;
@@ -295,46 +248,42 @@ struct StreamWave {
     // kStage: rows are prefetched straight to LDS (buffer_load_dword ... lds), not to registers: a second prefetch
     // buffer of R x M VGPRs -- with the seam lane's extra half-block -- spilled the (12, 2) pass at its 168-VGPR
     // budget.  The trip reads its rows back at its top, after the wait, so a bounded board's row masks apply there
-    // and never make a trip wait for its own prefetch.  kSeam: per row and word a second dword load lands in the
-    // stage, the word at seam_off -- for the seam lane the block left of lane 0, for every other lane its own word
-    // again (a cache hit) -- and each lane takes the high half of its word from it: a no-op except on the seam lane.
-    int seam_off = 0;
-    // M dword LDS-DMAs per row and kind.  (One dwordx3 DMA per row at M = 2 -- there is no dwordx2 form -- saves 8
-    // instructions per trip but strides the stage 12 bytes per lane: the LDS reads then need more address registers
-    // than the (12, 2) pass has, and it spilled.)
-    static constexpr int kDmaWords = 1;  // dwords per lane per DMA
-    static constexpr int kDmas = M;      // DMAs per row and kind
-    using Stage = uint32_t[2][kSeam && !kSeam1 ? 2 : 1][R][kDmas][kWave * kDmaWords];  // [parity][row, seam][row][dma][lane x words]
+    // and never make a trip wait for its own prefetch.  One dword LDS-DMA per lane, M per row.
+    // CODE-GENERATION PINS: pin_off, pin_stage and pin_pitch below are READ BY NOTHING.  They stand where the removed
+    // seam DMAs kept a lane offset, an LDS slot pointer and a row delta, and the seam passes still store to them (the
+    // constructor and the kernel, `if constexpr (kSeam)`); the compiler deletes all of it.  But how it splits this
+    // object into registers follows the object's zero-initialised runs and its stores: without these three the
+    // bounded trip loops pick another induction variable, the seam passes order their kernel-argument loads and
+    // scalar multiplies differently and the level windows land in other registers -- the same instruction counts in
+    // another order, in 76 of the 97 kernels, on passes whose speed has followed such changes before (DESIGN.md 4.1,
+    // round 3 "Measured and rejected").  profiles/step_arms/README.md has the search that left these three.  They go
+    // with the next change that is allowed to alter the device code, and is measured.
+    int pin_off = 0;
+    using Stage = uint32_t[2][R][M][kWave];  // [parity][row][word][lane]
     Stage* stage = nullptr;
-    // kSeam1: the per-trip seam slot [parity][lane], this lane's row (relative to the trip's first) and byte offset in
-    // the seam DMA, and the seam lane's merge mask (0xffff0000 on the seam lane of a seam strip, 0 elsewhere: remainder
-    // waves and halo-lane strips merge nothing)
-    using SeamStage = uint32_t[2][kWave];
-    SeamStage* seam1 = nullptr;
-    // GOL_SEAM_SMEM: the next trip's seam words (SGPRs), the seam column's byte offset in a row, and whether this wave
-    // merges a seam (a seam strip, not a remainder wave)
-    static constexpr bool kSmem = kSeam1 && GOL_SEAM_SMEM;
+    Stage* pin_stage = nullptr;
+    // kSeam: the seam lane's half-blocks come by the scalar unit -- the R x M seam words of a trip are the same for
+    // every lane, so each row's M words are one s_load into SGPRs (`sm.s`), issued at the END of the previous trip, when
+    // its row DMAs have brought those lines (the seam block sits beside lane 0's) into L2.  (The board buffer a pass
+    // reads is never written during it: the scalar cache, refilled at every dispatch, holds no stale line.)
+    // `sm`: the next trip's seam words and buffer rows, the seam column in a row, and whether this wave merges a seam (a
+    // seam strip, not a remainder wave).  `hmask`: the merge mask of stage_in, 0xffff0000 on the seam lane of a seam
+    // strip, 0 elsewhere (remainder waves and halo-lane strips merge nothing).
     struct SmemSeam {
         uint32_t s[R][M];
         int64_t col;  // in words
         bool on;
-        int64_t row[R];  // GOL_SEAM_SMEM 2: the buffer rows of the next trip, loaded at the trip's end
+        int64_t row[R];
     };
     struct NoSmem {};
-    [[no_unique_address]] typename std::conditional<kSmem, SmemSeam, NoSmem>::type sm;
-    int seam1_delta = 0;  // (lane / M) % R rows + the word (lane % M) of the block left of lane 0, in bytes
+    [[no_unique_address]] typename std::conditional<kSeam, SmemSeam, NoSmem>::type sm;
+    int pin_pitch = 0;
     uint32_t hmask = 0;
-    template <int WORDS>
     __device__ __forceinline__ static void dma(__amdgpu_buffer_rsrc_t rs, uint32_t* lds, int off) {
         auto* p = (__attribute__((address_space(3))) void*)lds;
-        if constexpr (WORDS == 3)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, p, 12, off, 0, 0, 0);
-        else
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, p, 4, off, 0, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, p, 4, off, 0, 0, 0);
     }
-    __device__ __forceinline__ uint32_t staged(int par, int kind, int r, int j, int lane) const {
-        return kDmas == 1 ? (*stage)[par][kind][r][0][lane * kDmaWords + j] : (*stage)[par][kind][r][j][lane];
-    }
+    __device__ __forceinline__ uint32_t staged(int par, int r, int j, int lane) const { return (*stage)[par][r][j][lane]; }
     int64_t seg_begin, seg_end, nsteps, ly0;
     __device__ __forceinline__ int64_t buf_bytes() const { return (a.rows + 2 * a.ghost) * a.pitch * 4; }
     __device__ __forceinline__ __amdgpu_buffer_rsrc_t src_rs(const uint32_t* base, int64_t bytes, int tag) const {
@@ -485,8 +434,7 @@ struct StreamWave {
                 if (lane < kSeamInterior) {
                     load_off = store_off = (int)(floor_mod(b, nblocks) * 4 * M);
                 } else {
-                    load_off = (int)(floor_mod(b, nblocks) * 4 * M);                          // right of lane 62
-                    seam_off = (int)(floor_mod(sx * kSeamInterior - 1, nblocks) * 4 * M);     // left of lane 0
+                    load_off = (int)(floor_mod(b, nblocks) * 4 * M);  // right of lane 62 (left of lane 0: sm.col)
                     store_off = kNoStore;
                 }
             } else if (a.seam) {  // remainder wave: sub-strip j = lane / (rem + 2) on segment sy + j
@@ -498,20 +446,15 @@ struct StreamWave {
                 store_off = (j < rem_count && i >= 1 && i <= a.rem) ? load_off : kNoStore;
                 span_bytes = (int64_t)(rem_count - 1) * a.seg * a.pitch * 4 + row_bytes;
             }
-            if (lane < kSeamInterior || !a.seam || rem_count) seam_off = load_off;
-            if constexpr (kSeam1) {
-                seam1_delta = (int)(((lane / M) % R) * a.pitch * 4) + 4 * (lane % M) +
-                              (a.seam && rem_count == 0 ? (int)(floor_mod(sx * kSeamInterior - 1, nblocks) * 4 * M) : 0);
-                hmask = a.seam && rem_count == 0 && lane == kWave - 1 ? 0xffff0000u : 0u;
-                if constexpr (kSmem) {
-                    sm.on = a.seam && rem_count == 0;
-                    sm.col = sm.on ? floor_mod(sx * kSeamInterior - 1, nblocks) * M : 0;
+            pin_off = load_off;  // (code-generation pins: see pin_off)
+            pin_pitch = (int)a.pitch;
+            hmask = a.seam && rem_count == 0 && lane == kWave - 1 ? 0xffff0000u : 0u;
+            sm.on = a.seam && rem_count == 0;
+            sm.col = sm.on ? floor_mod(sx * kSeamInterior - 1, nblocks) * M : 0;
 #pragma unroll
-                    for (int r = 0; r < R; r++)
+            for (int r = 0; r < R; r++)
 #pragma unroll
-                        for (int j = 0; j < M; j++) sm.s[r][j] = 0u;
-                }
-            }
+                for (int j = 0; j < M; j++) sm.s[r][j] = 0u;
         }
         seg_begin = a.out_begin + sy * a.seg;
         seg_end = seg_begin + a.seg < a.out_end ? seg_begin + a.seg : a.out_end;
@@ -558,7 +501,7 @@ struct StreamWave {
         }
         if constexpr (kStage) {
             const uint64_t pitch_bytes = (uint64_t)a.pitch * 4;
-            if (BOUNDED || (GOL_AB_WRAPPTR && WRAP_ROWS))
+            if (BOUNDED)
                 lptr = (uint64_t)(uintptr_t)src + (uint64_t)load_br * pitch_bytes;  // (bounded: may precede the buffer)
             sd = -R - 2 * K;  // the first store (at trip 0's top) is trip -1's: nothing valid
             sptr = (uint64_t)(uintptr_t)dst + (uint64_t)((WRAP_ROWS ? 0 : a.ghost) + seg_begin + sd) * pitch_bytes;
@@ -618,103 +561,50 @@ struct StreamWave {
     template <int PAR>
     __device__ __forceinline__ void stage_load() {
 #pragma unroll
-        for (int r = 0; r < R; r++) stage_load_row<PAR, 3>(r);
+        for (int r = 0; r < R; r++) stage_load_row<PAR>(r);
     }
-    // KINDS: 1 = the row's own-word DMAs (advancing the row walk; the descriptor is kept for the seam DMAs), 2 = its
-    // seam DMAs (kept descriptor), 3 = both
-    __amdgpu_buffer_rsrc_t row_rs[R];
-    // kSeam1: the trip's one seam DMA, issued with its first row (buffer row br0, wave-uniform): lane i loads from row
-    // br0 + (i / M) % R through a range-checked descriptor based at row br0.  Ghost-row strips: rows past the buffer
-    // (only the tail trip's unused rows) read as 0.  Single board: a trip whose rows wrap past the board's last row
-    // (first and last segments) splits the lanes -- rows before the wrap from the descriptor at br0, the others from
-    // one based at row 0 -- so every lane reads its row.  No per-lane 64-bit address is formed.
-    template <int PAR>
-    __device__ __forceinline__ void stage_load_seam1(int64_t br0) {
-        const int64_t pb = a.pitch * 4;
-        uint32_t* lds = &(*seam1)[PAR][0];
-        const uint32_t* base = src + br0 * a.pitch;
-        if (WRAP_ROWS) {
-            if (br0 + R <= a.rows) {
-                dma<1>(src_rs(base, R * pb, 3), lds, seam1_delta);
-            } else {
-                const int n1 = (int)((a.rows - br0) * pb);  // bytes of the rows before the wrap (>= one row)
-                if (seam1_delta < n1)
-                    dma<1>(src_rs(base, n1, 4), lds, seam1_delta);
-                else
-                    dma<1>(src_rs(src, R * pb, 5), lds, seam1_delta - n1);
-            }
-        } else {
-            const int64_t left = (a.rows + 2 * a.ghost - br0) * pb;
-            dma<1>(src_rs(base, left < R * pb ? left : R * pb, 6), lds, seam1_delta);
-        }
-    }
-    // GOL_SEAM_SMEM: one scalar load of row r's M seam words (wave-uniform address)
+    // One scalar load of row r's M seam words (wave-uniform address)
     __device__ __forceinline__ void smem_seam_row(int r, int64_t br) {
-        if constexpr (kSmem) {
-            typedef uint32_t su32xM __attribute__((ext_vector_type(M)));
-            const auto* q = (const __attribute__((address_space(4))) su32xM*)(uintptr_t)(src + br * a.pitch + sm.col);
-            const su32xM x = *q;
+        typedef uint32_t su32xM __attribute__((ext_vector_type(M)));
+        const auto* q = (const __attribute__((address_space(4))) su32xM*)(uintptr_t)(src + br * a.pitch + sm.col);
+        const su32xM x = *q;
 #pragma unroll
-            for (int j = 0; j < M; j++) sm.s[r][j] = x[j];
-        }
+        for (int j = 0; j < M; j++) sm.s[r][j] = x[j];
     }
-    // GOL_SEAM_SMEM 2: the next trip's seam words at the end of this trip, when its row DMAs have filled the lines
+    // kSeam: the next trip's seam words at the end of this trip, when its row DMAs have filled the lines
     __device__ __forceinline__ void smem_seam_late() {
-        if constexpr (kSmem && GOL_SEAM_SMEM == 2) {
+        if constexpr (kSeam) {
             if (sm.on) {
 #pragma unroll
                 for (int r = 0; r < R; r++) smem_seam_row(r, sm.row[r]);
             }
         }
     }
-    template <int PAR, int KINDS>
+    // Row r of the prefetch: advances the row walk and issues the row's M DMAs (kSeam: notes its buffer row for
+    // smem_seam_late)
+    template <int PAR>
     __device__ __forceinline__ void stage_load_row(int r) {
-        if constexpr ((KINDS & 1) == 0) {
-#pragma unroll
-            for (int d = 0; d < kDmas; d++)
-                if constexpr (kSeam && !kSeam1) dma<kDmaWords>(row_rs[r], &(*stage)[PAR][kSeam ? 1 : 0][r][d][0], seam_off + 4 * d);
+        __amdgpu_buffer_rsrc_t rs;
+        if constexpr (BOUNDED) {
+            const bool inside = lrow >= step_lo && lrow <= step_hi;
+            rs = src_rs(reinterpret_cast<const uint32_t*>(lptr), inside ? span_bytes : 0, 7);
+            lptr += (uint64_t)a.pitch * 4;
+            lrow++;
         } else {
-            __amdgpu_buffer_rsrc_t rs;
-            if constexpr (BOUNDED) {
-                const bool inside = lrow >= step_lo && lrow <= step_hi;
-                rs = src_rs(reinterpret_cast<const uint32_t*>(lptr), inside ? span_bytes : 0, 7);
-                lptr += (uint64_t)a.pitch * 4;
-                lrow++;
+            int64_t br = load_br;
+            if (WRAP_ROWS) {
+                load_br = br + 1 == a.rows ? 0 : br + 1;
             } else {
-                int64_t br = load_br;
-                [[maybe_unused]] const uint64_t p = lptr;
-                if (WRAP_ROWS) {
-                    load_br = br + 1 == a.rows ? 0 : br + 1;
-                    if constexpr (GOL_AB_WRAPPTR) lptr = load_br == 0 ? (uint64_t)(uintptr_t)src : p + (uint64_t)a.pitch * 4;
-                } else {
-                    const int64_t buf_rows = a.rows + 2 * a.ghost;
-                    load_br = br + 1;
-                    br = br < 0 ? 0 : (br < buf_rows ? br : buf_rows - 1);
-                }
-                rs = src_rs(GOL_AB_WRAPPTR && WRAP_ROWS ? reinterpret_cast<const uint32_t*>(p) : src + br * a.pitch, span_bytes, 8);
-                if constexpr (kSmem && GOL_SEAM_SMEM == 2) {
-                    sm.row[r] = br;
-                } else if constexpr (kSmem) {
-                    if (sm.on) smem_seam_row(r, br);
-                } else if constexpr (kSeam1 && !GOL_AB_NOSEAMDMA) {
-                    if (r == 0) stage_load_seam1<PAR>(br);
-                }
+                const int64_t buf_rows = a.rows + 2 * a.ghost;
+                load_br = br + 1;
+                br = br < 0 ? 0 : (br < buf_rows ? br : buf_rows - 1);
             }
-            if constexpr ((KINDS & 2) == 0 && !kSeam1) row_rs[r] = rs;
-#pragma unroll
-            for (int d = 0; d < kDmas; d++) {
-                dma<kDmaWords>(rs, &(*stage)[PAR][0][r][d][0], load_off + 4 * d);
-                if constexpr (kSeam && !kSeam1 && (KINDS & 2))
-                    dma<kDmaWords>(rs, &(*stage)[PAR][kSeam ? 1 : 0][r][d][0], seam_off + 4 * d);
-            }
+            rs = src_rs(src + br * a.pitch, span_bytes, 8);
+            if constexpr (kSeam) sm.row[r] = br;
         }
+#pragma unroll
+        for (int j = 0; j < M; j++) dma(rs, &(*stage)[PAR][r][j][0], load_off + 4 * j);
     }
-    // kStage, after the wait for stage parity PAR and the previous trip's stores: read the trip's words from the stage
-    // straight into the row buffer (and the seam words), before the next prefetch is issued, so the LDS latency
-    // hides behind it ...
-    struct Seam {
-        uint32_t s[kSeam ? R : 1][M];
-    };
     // kStage: store the previous trip's R output rows (running store address; rows outside the segment -- the
     // pipeline fill and the tail -- get an empty descriptor and are dropped)
     __device__ __forceinline__ void store_staged(const uint32_t (&v)[R][M]) {
@@ -729,50 +619,28 @@ struct StreamWave {
         sptr += R * pitch_bytes;
         sd += R;
     }
+    // kStage, after the wait for stage parity PAR and the previous trip's stores: read the trip's words from the stage
+    // straight into the row buffer, before the next prefetch is issued, so the LDS latency hides behind it ...
     template <int PAR>
     __device__ __forceinline__ void stage_read(uint32_t (&v)[R][M], int lane) {
 #pragma unroll
         for (int r = 0; r < R; r++)
 #pragma unroll
-            for (int j = 0; j < M; j++) v[r][j] = staged(PAR, 0, r, j, lane);
+            for (int j = 0; j < M; j++) v[r][j] = staged(PAR, r, j, lane);
     }
-    template <int PAR>
-    __device__ __forceinline__ void stage_read_seam(Seam& t, int lane) {
-        if constexpr (kSeam1 && GOL_AB_NOSEAMDMA) {
-        } else if constexpr (kSmem) {
-#pragma unroll
-            for (int r = 0; r < R; r++)
-#pragma unroll
-                for (int j = 0; j < M; j++) t.s[r][j] = sm.s[r][j];
-        } else if constexpr (kSeam1) {  // the same R x M words for every lane (a broadcast read)
-#pragma unroll
-            for (int r = 0; r < R; r++)
-#pragma unroll
-                for (int j = 0; j < M; j++) t.s[r][j] = (*seam1)[PAR][r * M + j];
-        } else if constexpr (kSeam) {
-#pragma unroll
-            for (int r = 0; r < R; r++)
-#pragma unroll
-                for (int j = 0; j < M; j++) t.s[r][j] = staged(PAR, kSeam ? 1 : 0, r, j, lane);
-        }
-    }
-    // ... and make them the rows of steps first_step ..: kSeam, each word's high half from the seam word; bounded, rows
-    // off the board (and, NARROW, columns off it) dead (Script.fsx:11).
-    __device__ __forceinline__ void stage_in(uint32_t (&v)[R][M], const Seam& t, int64_t first_step) {
+    // ... and make them the rows of steps first_step ..: kSeam, each word's high half from the seam word (`hmask`: a
+    // no-op except on the seam lane; sm.s is the previous trip's smem_seam_late, which nothing overwrites before the
+    // end of this trip); bounded, rows off the board (and, NARROW, columns off it) dead (Script.fsx:11).
+    __device__ __forceinline__ void stage_in(uint32_t (&v)[R][M], int64_t first_step) {
         (void)first_step;
-        (void)t;
 #pragma unroll
         for (int r = 0; r < R; r++) {
             [[maybe_unused]] uint32_t rm = 0xffffffffu;
             if constexpr (BOUNDED) rm = row_mask((int)first_step + r);
 #pragma unroll
             for (int j = 0; j < M; j++) {
-                if constexpr (kSeam1 && GOL_AB_NOSEAMDMA)
-                    ;
-                else if constexpr (kSeam1)
-                    v[r][j] = lut3<0xD8>(hmask, t.s[kSeam ? r : 0][j], v[r][j]);
-                else if constexpr (kSeam)
-                    v[r][j] = lut3<0xD8>(0xffff0000u, t.s[kSeam ? r : 0][j], v[r][j]);
+                if constexpr (kSeam)
+                    v[r][j] = lut3<0xD8>(hmask, sm.s[r][j], v[r][j]);
                 else if constexpr (BOUNDED)
                     v[r][j] = kColMask || kRagEdge ? lut3<0x80>(v[r][j], colmask[j], rm) : v[r][j] & rm;
             }
@@ -1003,85 +871,45 @@ void gol_stream_step(const uint32_t* __restrict__ src, uint32_t* __restrict__ ds
         // trip earlier (the wait-count pass treats pending loads and stores as completing out of order).
         __shared__ typename W::Stage stage[WPB];
         w.stage = &stage[wave];
-        __shared__ uint32_t seam1_stage[W::kSeam1 ? WPB : 1][2][W::kSeam1 ? kWave : 1];
-        if constexpr (W::kSeam1) w.seam1 = &seam1_stage[wave];
+        if constexpr (W::kSeam) w.pin_stage = &stage[wave];  // (code-generation pin: see StreamWave::pin_off)
         uint32_t NV[R];  // (K = 1 neighbour words: unused here)
 #pragma unroll
         for (int r = 0; r < R; r++) NV[r] = 0;
         w.template stage_load<0>();
-        w.smem_seam_late();  // (GOL_SEAM_SMEM 2: trip 0's seam words)
+        w.smem_seam_late();  // (trip 0's seam words)
         auto trip = [&](int64_t tt, auto skip, auto mask, auto par) {
             constexpr int PAR = decltype(par)::value;
             __builtin_amdgcn_s_waitcnt(kWaitVm0);
             w.store_staged(B);
             w.template stage_read<PAR>(B, lane);
-            // (GOL_SEAM_SMEM: the seam words taken before this trip's prefetch loads the next trip's over them)
-            [[maybe_unused]] typename W::Seam st_smem;
-            if constexpr (W::kSmem) w.template stage_read_seam<PAR>(st_smem, lane);
             __builtin_amdgcn_sched_barrier(0);  // the row reads before the prefetch: their latency hides behind it
-            // prefetch placement (GOL_SEAM_SPREAD above): rows issued at the top, after level g, and after the levels
-            // (the pipeline-fill trips, which skip levels, keep every DMA at the top)
-            constexpr int kSpread = GOL_SEAM_SPREAD >= 0 ? GOL_SEAM_SPREAD : 4;
-            constexpr int kMode = (W::kSeam || (BOUNDED && GOL_AB_BSPREAD)) && !decltype(skip)::value ? kSpread : 0;
-            if constexpr (kMode == 0) w.template stage_load<1 - PAR>();
-            if constexpr (kMode == 3) {
-#pragma unroll
-                for (int r = 0; r < R; r++) w.template stage_load_row<1 - PAR, 1>(r);
-            }
-            typename W::Seam st;
-            if constexpr (W::kSmem)
-                st = st_smem;
-            else
-                w.template stage_read_seam<PAR>(st, lane);
-            w.stage_in(B, st, tt * R);
+            // Prefetch placement.  Seam passes outside the pipeline-fill trips (which skip levels) spread the next
+            // trip's rows over this trip's levels: row r's DMAs go out after level 2r, and the rows a pass of K < 2R
+            // levels has not issued by its last level follow after it.  Everywhere else all R rows' DMAs go at the
+            // trip's top: spreading lost 5 % on the bounded passes (profiles/r3/ab_spread_h.log).
+            // This is "mode 4" of the logs (there with a seam DMA after level 2r + 1, where nothing is loaded now).
+            // The modes it was measured against: 0 = everything at the top, 1 = one row's own and seam DMAs after
+            // each of the first R levels, 3 = own-word DMAs at the top and one row's seam DMAs after each of the first
+            // R levels, 5 = as 4 but every 3 levels (profiles/r3/ab_spread_modes_i.log, profiles/r4/ab_spread_o.log,
+            // ab_spread5_q.log).
+            constexpr bool kSpread = W::kSeam && !decltype(skip)::value;
+            if constexpr (!kSpread) w.template stage_load<1 - PAR>();
+            w.stage_in(B, tt * R);
             __builtin_amdgcn_sched_barrier(0);  // keep the prefetch at the top of the trip
-            auto hook = [&](int g) {
-                if constexpr (kMode == 1 || kMode == 3) {
-                    if (g < R) {
-                        w.template stage_load_row<1 - PAR, kMode == 1 ? 3 : 2>(g);
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                } else if constexpr (kMode == 4) {
+            auto hook = [&](int g) {  // after level g
+                if constexpr (kSpread) {
                     if (g < 2 * R) {
-                        if (g % 2 == 0)
-                            w.template stage_load_row<1 - PAR, 1>(g / 2);
-                        else
-                            w.template stage_load_row<1 - PAR, 2>(g / 2);
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                } else if constexpr (kMode == 5) {  // A/B: row r's DMAs after levels 3r and 3r + 1
-                    if (g < 3 * R && g % 3 < 2) {
-                        if (g % 3 == 0)
-                            w.template stage_load_row<1 - PAR, 1>(g / 3);
-                        else
-                            w.template stage_load_row<1 - PAR, 2>(g / 3);
-                        __builtin_amdgcn_sched_barrier(0);
+                        if (g % 2 == 0) w.template stage_load_row<1 - PAR>(g / 2);
+                        __builtin_amdgcn_sched_barrier(0);  // (after the odd levels too: part of the measured schedule)
                     }
                 }
             };
             w.template process<decltype(skip)::value, decltype(mask)::value>(B, NV, tt, hook);
-            // a pass shallower than the levels the mode spreads over: the rows not yet issued
-            if constexpr (kMode == 1 || kMode == 3) {
+            if constexpr (kSpread) {
 #pragma unroll
-                for (int r = K; r < R; r++) w.template stage_load_row<1 - PAR, kMode == 1 ? 3 : 2>(r);
-            } else if constexpr (kMode == 4) {
-#pragma unroll
-                for (int g = K; g < 2 * R; g++) {
-                    if (g % 2 == 0)
-                        w.template stage_load_row<1 - PAR, 1>(g / 2);
-                    else
-                        w.template stage_load_row<1 - PAR, 2>(g / 2);
-                }
-            } else if constexpr (kMode == 5) {
-#pragma unroll
-                for (int g = K; g < 3 * R; g++) {
-                    if (g % 3 == 0)
-                        w.template stage_load_row<1 - PAR, 1>(g / 3);
-                    else if (g % 3 == 1)
-                        w.template stage_load_row<1 - PAR, 2>(g / 3);
-                }
+                for (int r = (K + 1) / 2; r < R; r++) w.template stage_load_row<1 - PAR>(r);
             }
-            w.smem_seam_late();  // (GOL_SEAM_SMEM 2)
+            w.smem_seam_late();
         };
         using Mask = std::true_type;
         using NoMask = std::false_type;
@@ -1120,18 +948,19 @@ void gol_stream_step(const uint32_t* __restrict__ src, uint32_t* __restrict__ ds
         }
         __builtin_amdgcn_s_waitcnt(kWaitVm0);
         w.store_staged(B);
-    } else if constexpr (!BOUNDED) {
+    } else {
         // K = 1 (rows of trip t in `cur`, trip t-1's outputs in `other`):
         //   [wait for all memory ops of trip t-1] [store `other`] [prefetch trip t+1 into `other`]
         //   [compute trip t in place in `cur`]
-        // the two row buffers alternate roles (A/B) so no register copy or early wait joins a prefetch.
+        // the two row buffers alternate roles (A/B) so no register copy or early wait joins a prefetch.  On a bounded
+        // board every trip masks (halo-free strips carry per-lane column masks).
         auto trip = [&](uint32_t (&cur)[R][M], uint32_t (&other)[R][M], uint32_t (&ncur)[R], uint32_t (&nother)[R],
                         int64_t tt, auto skip) {
             __builtin_amdgcn_s_waitcnt(kWaitVm0);
             w.store_masked(other, tt - 1);
             w.load(other, nother, (tt + 1) * R);
             __builtin_amdgcn_sched_barrier(0);  // keep the prefetch at the top of the trip
-            w.template process<decltype(skip)::value, false>(cur, ncur, tt);
+            w.template process<decltype(skip)::value, BOUNDED>(cur, ncur, tt);
         };
         for (int64_t p = 0; p < fill_pairs; p++, t += 2) {
             trip(A, B, NA, NB, t, Skip{});
@@ -1142,32 +971,6 @@ void gol_stream_step(const uint32_t* __restrict__ src, uint32_t* __restrict__ ds
             trip(B, A, NB, NA, t + 1, NoSkip{});
         }
         if (t < ntrips) {  // odd trip count: one more trip, outputs land in A
-            trip(A, B, NA, NB, t, NoSkip{});
-            __builtin_amdgcn_s_waitcnt(kWaitVm0);
-            w.store_masked(A, t);
-        } else {
-            __builtin_amdgcn_s_waitcnt(kWaitVm0);
-            w.store_masked(B, t - 1);
-        }
-    } else {
-        // K = 1 on a bounded board: every trip masks (halo-free strips carry per-lane column masks)
-        auto trip = [&](uint32_t (&cur)[R][M], uint32_t (&other)[R][M], uint32_t (&ncur)[R], uint32_t (&nother)[R],
-                        int64_t tt, auto skip) {
-            __builtin_amdgcn_s_waitcnt(kWaitVm0);
-            w.store_masked(other, tt - 1);
-            w.load(other, nother, (tt + 1) * R);
-            __builtin_amdgcn_sched_barrier(0);  // keep the prefetch at the top of the trip
-            w.template process<decltype(skip)::value, true>(cur, ncur, tt);
-        };
-        for (int64_t p = 0; p < fill_pairs; p++, t += 2) {
-            trip(A, B, NA, NB, t, Skip{});
-            trip(B, A, NB, NA, t + 1, Skip{});
-        }
-        for (; t + 1 < ntrips; t += 2) {
-            trip(A, B, NA, NB, t, NoSkip{});
-            trip(B, A, NB, NA, t + 1, NoSkip{});
-        }
-        if (t < ntrips) {
             trip(A, B, NA, NB, t, NoSkip{});
             __builtin_amdgcn_s_waitcnt(kWaitVm0);
             w.store_masked(A, t);
@@ -1207,19 +1010,6 @@ bool stream_supported(int k, int ilv) {
     return ilv == 4 && pipe_supported(k);
 }
 
-int stream_max_k(int ilv) { return ilv == 1 ? 32 : (ilv == 2 ? 16 : 32); }
-
-int stream_largest_k(int64_t n, int cap, int ilv, int64_t words, bool bounded) {
-    static const int ks[] = {32, 24, 16, 12, 8, 6, 4, 2, 1};
-    for (int k : ks) {
-        if (k > cap || k > n || !stream_supported(k, ilv)) continue;
-        // the level-pipelined depths (16 / 32 at ilv 4) only where that pass runs (torus rows of a full strip)
-        if (ilv == 4 && pipe_supported(k) && !pipe_applies(words, ilv, k, bounded, 0)) continue;
-        return k;
-    }
-    return 1;
-}
-
 // The NARROW template value of a pass.  Torus: 1 = the M = 1 ragged-row variant (StreamWave kRagged).  Bounded: 1 = a
 // board narrower than one wave strip (halo-lane strips, column masks at every level), 2 = a ragged row (rag_bits: the
 // board's width is not a multiple of 32; a.rag_w) at least a strip wide (edge-fill strips, column masks at every
@@ -1231,91 +1021,47 @@ static int stream_narrow(int64_t words, int ilv, int k, bool bounded, int rag_bi
     return rag_bits != 0 ? 2 : 0;
 }
 
-// Variants: torus with rows wrapping in the buffer (single board), torus strip with ghost rows, ragged torus rows
-// (single board, ilv 1), bounded (never wraps: rows beyond the board are masked dead; narrow and ragged boards
-// mask columns too).
+// The variant table: the one place that maps a pass to its gol_stream_step instantiation and that instantiation's
+// waves per workgroup (Wpb).  Variants: torus with rows wrapping in the buffer (single board), torus strip with ghost
+// rows, ragged torus rows (single board, ilv 1), bounded (never wraps: rows beyond the board are masked dead; narrow
+// and ragged boards mask columns too).  fn is null where no kernel exists: an unsupported (K, M), or ragged torus
+// rows at M != 1 or on a ghost-row strip.
+struct Variant {
+    const void* fn;
+    int wpb;
+};
+template <int K, int M, bool BOUNDED, bool WRAP_ROWS, int NARROW>
+static Variant variant() {
+    return {(const void*)&gol_stream_step<K, M, BOUNDED, WRAP_ROWS, NARROW>, Wpb<K, M, BOUNDED, WRAP_ROWS, NARROW>::value};
+}
 template <int K, int M>
-static const void* stream_kernel(bool bounded, bool wrap, int narrow) {
+static Variant variant_km(bool bounded, bool wrap, int narrow) {
     if (bounded)
-        return narrow == 1 ? (const void*)&gol_stream_step<K, M, true, false, 1>
-                           : (narrow == 2 ? (const void*)&gol_stream_step<K, M, true, false, 2>
-                                          : (const void*)&gol_stream_step<K, M, true, false, 0>);
+        return narrow == 1 ? variant<K, M, true, false, 1>()
+                           : (narrow == 2 ? variant<K, M, true, false, 2>() : variant<K, M, true, false, 0>());
     if (narrow) {
-        if constexpr (M == 1) return wrap ? (const void*)&gol_stream_step<K, 1, false, true, 1> : nullptr;
-        return nullptr;
+        if constexpr (M == 1)
+            if (wrap) return variant<K, 1, false, true, 1>();
+        return {nullptr, kWavesPerBlock};
     }
-    return wrap ? (const void*)&gol_stream_step<K, M, false, true, 0>
-                : (const void*)&gol_stream_step<K, M, false, false, 0>;
+    return wrap ? variant<K, M, false, true, 0>() : variant<K, M, false, false, 0>();
 }
-
-static const void* kernel_for(int k, int ilv, bool bounded, bool wrap, int narrow) {
-#define GOL_KPTR(K_, M_) \
-    if (k == K_ && ilv == M_) return stream_kernel<K_, M_>(bounded, wrap, narrow);
-    GOL_FOR_EACH_KM(GOL_KPTR)
-#undef GOL_KPTR
-    return nullptr;
-}
-
-int64_t stream_strips(int64_t words, int ilv, int k, bool bounded, int rag_bits) {
-    const int64_t nblocks = words / ilv;
-    if (rag_bits && !bounded) return (nblocks + kInterior - 1) / kInterior;  // ragged torus rows: see plan_stream
-    if (k == 1) return (nblocks + kWave - 1) / kWave;  // K = 1: halo-free strips
-    // bounded edge-fill strips (StreamWave::edge_fill): strip 0 stores blocks [0, 63), strip s stores
-    // [62 s + 1, 62 s + 63), the last ends at the board's last block
-    if (bounded && nblocks >= kWave) return (nblocks - 1 + kInterior - 1) / kInterior;
-    // halo-lane strips (torus; bounded NARROW = 1: narrow rows): strip s stores blocks [62 s, 62 s + 62)
-    return (nblocks + kInterior - 1) / kInterior;
+static Variant variant_for(int k, int ilv, bool bounded, bool wrap, int narrow) {
+#define GOL_VARIANT(K_, M_) \
+    if (k == K_ && ilv == M_) return variant_km<K_, M_>(bounded, wrap, narrow);
+    GOL_FOR_EACH_KM(GOL_VARIANT)
+#undef GOL_VARIANT
+    return {nullptr, kWavesPerBlock};
 }
 
 // Waves per workgroup of a variant (Wpb)
 int stream_wpb(int64_t words, int k, int ilv, bool bounded, bool wrap, int rag_bits) {
-    const int narrow = stream_narrow(words, ilv, k, bounded, rag_bits);
-#define GOL_WPBQ(K_, M_)                                                                                 \
-    if (k == K_ && ilv == M_)                                                                            \
-        return bounded ? (narrow == 1 ? Wpb<K_, M_, true, false, 1>::value                               \
-                                      : (narrow == 2 ? Wpb<K_, M_, true, false, 2>::value : Wpb<K_, M_, true, false, 0>::value)) \
-                       : (narrow ? Wpb<K_, M_, false, true, 1>::value                                     \
-                                 : (wrap ? Wpb<K_, M_, false, true, 0>::value : Wpb<K_, M_, false, false, 0>::value));
-    GOL_FOR_EACH_KM(GOL_WPBQ)
-#undef GOL_WPBQ
-    return kWavesPerBlock;
-}
-
-// Pair split (1/65536 units): the share of a pair segment given to the older of the two waves that
-// share a SIMD.  VALU issue favours the older wave (MI355X_MICROARCH.md "Two waves per SIMD"), so with
-// equal segments it finishes early and leaves the younger alone at the single-wave issue rate
-// (tools/tail.py: 65536^2, K = 16 -- waves 0-3 of every workgroup busy 489 us, waves 4-7 747 us).
-// A board's "split" option (gol_set_option) overrides it for experiments.
-int stream_pair_split(int k, int ilv, bool bounded, bool wrap, bool single) {
-    if (kWavesPerBlock < 8) return 0;
-    // Round 5, with the middle wave's share set apart (stream_split2), at the bench window (generation 300+), 4
-    // interleaved rounds (profiles/r5/split2_confirm_g.jsonl, us per pass, mean): single-board torus (12, 2) 0.66 / 0.76
-    // 442.5 against 0.70 / geometric 445.8; bounded (12, 2) 0.60 / 0.72 431.0 against 0.64 / geometric 436.0.  The
-    // per-role tails of a stamped build (profiles/r5/split2_tails_f.jsonl): torus roles ending at 439 / 378 / 436 us with
-    // geometric shares, 440 / 417 / 430 with 0.68 / 0.76.  Both retunes were measured on single boards only, so the
-    // ghost-row strips of N > 1 keep round 4's measured split on either boundary (`single`: one strip holding the whole
-    // board, ghost 0): torus strips fall through to 0.70 below, bounded strips keep 0.64.
-    if (bounded && ilv == 2 && k == 12) return (int)((single ? 0.60 : 0.64) * 65536);
-    if (!bounded && wrap && ilv == 2 && k == 12) return (int)(0.66 * 65536);
-    // measured at 65536^2 (profiles/r1/split_sweep*.log, two boxes): the deep passes gain 3-9 %; the
-    // shallow ones (short, memory-bound trips) are left unpaired
-    // (12, 2) runs 12-wave workgroups at 3 waves/SIMD: three-way groups (profiles/r1/w12_sweep*.log)
-    // Round 3, staged passes, fresh 65536^2 board, forward + reverse sweep (profiles/r3/split_sweep_f.log): torus
-    // (12, 2) 0.64 / 0.68 / 0.72 -> 95.9k / 96.8k / 95.0k; torus (16, 2) 0.60 / 0.64 / 0.68 / 0.72 -> 101.8k / 107.5k /
-    // 107.6k / 104.7k; bounded (12, 2) 0.60 / 0.64 / 0.68 -> 96.6k / 99.0k / 95.4k; bounded (16, 2) 0.56 / 0.60 /
-    // 0.64 / 0.68 -> 112.5k / 112.0k / 106.2k / 100.7k (a slope now, not round 2's cliff).
-    if (bounded && ilv == 2 && k == 16) return (int)(0.60 * 65536);
-    // (bounded (12, 2): 0.64 until round 5, above)
-    if (ilv == 1 && k >= 24) return (int)(0.60 * 65536);
-    if (ilv == 2 && k == 12) return (int)(0.70 * 65536);
-    if (ilv == 2 && k >= 16) return (int)(0.66 * 65536);
-    if (ilv == 4 && k >= 8) return (int)(0.55 * 65536);
-    return 0;
+    return variant_for(k, ilv, bounded, wrap, stream_narrow(words, ilv, k, bounded, rag_bits)).wpb;
 }
 
 // Waves of a stream-kernel variant the current device holds at once (occupancy x CUs), cached.  Falls back
 // to 4096 waves when no device answers (host-only planning, e.g. CPU tests).
-static int64_t resident_units(int64_t words, int k, int ilv, bool bounded, bool wrap, int rag_bits) {
+int64_t resident_units(int64_t words, int k, int ilv, bool bounded, bool wrap, int rag_bits) {
     static std::atomic<int64_t> cache[33][5][2][2][3];
     const int64_t fallback = 4096;
     if (k < 0 || k > 32 || ilv < 1 || ilv > 4) return fallback;
@@ -1323,182 +1069,19 @@ static int64_t resident_units(int64_t words, int k, int ilv, bool bounded, bool 
     const int narrow = stream_narrow(words, ilv, k, bounded, rag_bits);
     int64_t v = cache[k][ilv][bounded][wrap][narrow].load(std::memory_order_relaxed);
     if (v > 0) return v;
-    const void* fn = kernel_for(k, ilv, bounded, wrap, narrow);
-    const int wpb = stream_wpb(words, k, ilv, bounded, wrap, rag_bits);
-    const int threads = kWave * wpb;
+    const Variant var = variant_for(k, ilv, bounded, wrap, narrow);
+    const int threads = kWave * var.wpb;
     int dev = 0, cus = 0, blocks = 0;
-    if (!fn || hipGetDevice(&dev) != hipSuccess ||
+    if (!var.fn || hipGetDevice(&dev) != hipSuccess ||
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, fn, threads, 0) != hipSuccess || blocks <= 0 ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, var.fn, threads, 0) != hipSuccess || blocks <= 0 ||
         cus <= 0) {
         (void)hipGetLastError();
         return fallback;
     }
-    v = (int64_t)blocks * cus * wpb;
+    v = (int64_t)blocks * cus * var.wpb;
     cache[k][ilv][bounded][wrap][narrow].store(v, std::memory_order_relaxed);
     return v;
-}
-
-// Remainder units of the seam geometry for nsegs segments (kernel: the unit mapping in gol_stream_step).
-static int64_t seam_rem_units(const StreamArgs& a, int64_t nsegs, int64_t rem_mid) {
-    if (!a.seam || a.rem == 0 || nsegs <= 0) return 0;
-    return 1 + (rem_mid + a.rem_p - 1) / a.rem_p + (nsegs - 1 - rem_mid);
-}
-
-// Does the seam geometry apply?  Torus deep passes (the bounded edge-fill strips keep their zero-fill edges) on rows
-// of at least one seam strip, with K <= 16 M (the break in the middle of the seam lane must not reach its ends).
-static bool seam_applies(const StreamArgs& a, int k, bool bounded) {
-    return !GOL_AB_NOSEAM && a.seam_opt >= 0 && !bounded && !a.rag_bits && k > 1 && k <= 16 * a.ilv && a.words / a.ilv >= kSeamInterior;
-}
-
-// Work decomposition: nstrips column strips x nsegs row segments, one wave each (or one SIMD group of
-// waves per segment with the pair split), plus the seam geometry's remainder units.  The segment count makes the
-// grid ONE balanced round of resident waves (a partial second round would leave a tail of lone waves), with
-// segments no shorter than 2K rows (pipeline fill cost).  a.split_opt / a.seg_opt / a.seam_opt (a board's "split" /
-// "seg_rows" / "seam" options) override the split, the segment length and the geometry for experiments.
-// Three-wave groups: the middle wave's share of the two younger waves' rows (1/65536), 0 = geometric.
-int stream_split2(int k, int ilv, bool bounded, bool wrap, bool single) {
-    if (kWavesPerBlock < 8 || ilv != 2 || k != 12 || !single) return 0;  // (12, 2) single boards: see stream_pair_split
-    if (bounded) return (int)(0.72 * 65536);
-    return wrap ? (int)(0.76 * 65536) : 0;
-}
-
-void plan_stream(StreamArgs& a, int k, bool bounded, bool wrap) {
-    const bool single = a.ghost == 0 && a.rows == a.height;  // the whole board in one buffer (not a ghost-row strip)
-    a.split = a.split_opt > 0 ? a.split_opt : (a.split_opt < 0 ? 0 : stream_pair_split(k, a.ilv, bounded, wrap, single));
-    a.split2 = a.split2_opt > 0 ? a.split2_opt : stream_split2(k, a.ilv, bounded, wrap, single);
-    const int64_t nblocks = a.words / a.ilv;
-    a.seam = seam_applies(a, k, bounded) ? 1 : 0;
-    a.rem = 0;
-    a.rem_p = 1;
-    a.rem_units = 0;
-    a.rem_mid = 0;
-    if (a.seam) {
-        a.nstrips = nblocks / kSeamInterior;
-        a.rem = (int32_t)(nblocks - a.nstrips * kSeamInterior);
-        a.rem_p = a.rem ? (kWave / (a.rem + 2) > 0 ? kWave / (a.rem + 2) : 1) : 1;
-    } else {
-        a.nstrips = stream_strips(a.words, a.ilv, k, bounded, a.rag_bits);
-    }
-    // Ragged torus rows (StreamWave kRagged): the strips start at ring position -1 (the partial last word, then word
-    // 0, ...), unless the last strip's right halo lane would then be the partial word next to a stored word; then
-    // at position -2.
-    a.rag_origin = 1;
-    if (a.rag_bits && !bounded && (a.nstrips * kInterior - 1 + 1) % nblocks == 0) a.rag_origin = 2;
-    const int64_t rows = a.out_end - a.out_begin;
-    if (rows <= 0) {
-        a.nsegs = 0;
-        a.seg = 1;
-        return;
-    }
-    // a launch too short for one full group segment per strip (e.g. a k-row halo band) runs one wave per
-    // segment: splitting a handful of rows only multiplies the pipeline fill
-    const int wpb = stream_wpb(a.words, k, a.ilv, bounded, wrap, a.rag_bits);
-    if (a.split && rows < (int64_t)(wpb / 4) * (2 * k > 16 ? 2 * k : 16)) a.split = 0;
-    const int group = a.split ? wpb / 4 : 1;  // waves per segment
-    int64_t seg = a.seg_opt;
-    int64_t slots = 0;
-    if (seg <= 0) {
-        int64_t units = resident_units(a.words, k, a.ilv, bounded, wrap, a.rag_bits);
-        if (a.spare > 0) units = units > a.spare + 1 ? units - a.spare : 1;
-        slots = units / group;
-        // waves per segment: the strips, plus (seam geometry) a 1/rem_p share of a remainder wave
-        const double per_seg = (double)a.nstrips + (a.seam && a.rem ? 1.0 / a.rem_p : 0.0);
-        int64_t nsegs = (int64_t)((double)slots / per_seg);
-        if (nsegs < 1) nsegs = 1;
-        int64_t min_seg = (2 * k > 16 ? 2 * k : 16) * group;
-        // A launch too small to fill a quarter of the device is latency-bound: each wave is one serial
-        // chain of (segment + 2k) rows x k levels, so shorter segments (more, shorter chains) finish sooner
-        // despite the extra pipeline fill.  1024^2: 549 -> 696 GCUPS, 4096^2: 8.7k -> 10.5k at K = 8, ilv 1
-        // (profiles/r1/small_seg.log).  Large boards are bounded by `slots` below and do not change.
-        if ((rows / min_seg) * a.nstrips * group < units / 4) min_seg = (k > 8 ? k : 8) * group;
-        const int64_t max_segs = rows / min_seg > 0 ? rows / min_seg : 1;
-        if (nsegs > max_segs) nsegs = max_segs;
-        seg = (rows + nsegs - 1) / nsegs;
-    }
-    if (seg > ((int64_t)1 << 30)) seg = (int64_t)1 << 30;  // the kernel counts a segment's rows in 32 bits
-    a.seg = seg;
-    a.nsegs = (rows + seg - 1) / seg;
-    if (a.seam && a.rem) {
-        // the per-lane row offsets of a packed remainder wave are 32-bit byte offsets into one descriptor
-        const int64_t row_bytes = a.words * 4, step = seg * (a.pitch > 0 ? a.pitch : a.words) * 4;
-        const int64_t fit = 1 + ((((int64_t)1 << 31) - 1 - row_bytes) / step);
-        if (a.rem_p > fit) a.rem_p = (int32_t)(fit > 1 ? fit : 1);
-        // segments 1 .. rem_mid share remainder waves: every row they stream must lie in the board / buffer
-        // without a wrap.  Sub-strip j reads its rows at a fixed offset from sub-strip 0's walk, which wraps (single
-        // board) or clamps (ghost-row strip) only for itself; so the last packed segment's rows -- its k halo rows
-        // below and the walk's overshoot -- must end inside the buffer.  The walk prefetches whole trips of R = 4
-        // rows, one trip ahead, and the last trip prefetches one more (unused): ceil((seg + 2k) / 4) + 1 trips, up to
-        // 7 rows past the seg + 2k the segment streams.  Round 3 let those rows run past the buffer's end: reads
-        // beyond the allocation, harmless unless the next page was unmapped -- an illegal-address fault in round 4's
-        // suite on an 8209 x 40 ragged board (ring rows of 262 words, 42 KB), found by the GOL_CHECK_BOUNDS build
-        // (descriptor tag 8) and reproduced on the CPU by walking the plan.
-        const int64_t trip = 4;  // TripRows of every seam pass (K > 1)
-        const int64_t over = ((seg + 2 * k + trip - 1) / trip + 1) * trip - (seg + 2 * k);
-        const int64_t limit = wrap ? a.rows : a.rows + a.ghost;  // first row index past the buffer (owned-row units)
-        int64_t mid = a.nsegs - 2;
-        const int64_t fit_mid = (limit - a.out_begin - k - over) / seg - 1;  // (m + 1) seg + k + over <= limit - out_begin
-        if (fit_mid < mid) mid = fit_mid;
-        // sub-strip j streams rows [(j + 1) seg - k, (j + 2) seg + k) of the buffer at a fixed offset from
-        // sub-strip 0's walk: a segment shorter than k (the "seg_rows" option can ask for one) would make segment 1's
-        // first rows wrap or leave the buffer, so such segments run as lone remainder units
-        if (seg < k) mid = 0;
-        a.rem_mid = mid > 0 ? mid : 0;
-        a.rem_units = seam_rem_units(a, a.nsegs, a.rem_mid);
-    }
-}
-
-template <int K, int M>
-static hipError_t launch_km(const uint32_t* src, uint32_t* dst, const StreamArgs& a, bool bounded, bool wrap,
-                            hipStream_t s) {
-    const int WPB = stream_wpb(a.words, K, M, bounded, wrap, a.rag_bits);
-    const int64_t waves = (a.nstrips * a.nsegs + a.rem_units) * (a.split ? WPB / 4 : 1);
-    const unsigned blocks = (unsigned)((waves + WPB - 1) / WPB);
-    const dim3 block(kWave * WPB);
-    if (bounded) {
-        const int narrow = stream_narrow(a.words, M, K, true, a.rag_bits);
-        if (narrow == 1)
-            hipLaunchKernelGGL((gol_stream_step<K, M, true, false, 1>), dim3(blocks), block, 0, s, src, dst, a);
-        else if (narrow == 2)
-            hipLaunchKernelGGL((gol_stream_step<K, M, true, false, 2>), dim3(blocks), block, 0, s, src, dst, a);
-        else
-            hipLaunchKernelGGL((gol_stream_step<K, M, true, false, 0>), dim3(blocks), block, 0, s, src, dst, a);
-    } else if (a.rag_bits) {
-        if constexpr (M == 1) {
-            if (!wrap) return hipErrorInvalidValue;
-            hipLaunchKernelGGL((gol_stream_step<K, 1, false, true, 1>), dim3(blocks), block, 0, s, src, dst, a);
-        } else {
-            return hipErrorInvalidValue;
-        }
-    } else {
-        if (wrap)
-            hipLaunchKernelGGL((gol_stream_step<K, M, false, true, 0>), dim3(blocks), block, 0, s, src, dst, a);
-        else
-            hipLaunchKernelGGL((gol_stream_step<K, M, false, false, 0>), dim3(blocks), block, 0, s, src, dst, a);
-    }
-    return hipGetLastError();
-}
-
-PipeArgs pipe_args(const StreamArgs& a, bool bounded) {
-    PipeArgs p{};
-    p.words = a.words;
-    p.pitch = a.pitch;
-    p.rows = a.rows;
-    p.ghost = a.ghost;
-    p.out_begin = a.out_begin;
-    p.out_end = a.out_end;
-    p.split1 = a.pipe_split_opt;
-    p.split2 = a.pipe_split2_opt;
-    p.spare_waves = a.spare;
-    p.err = a.pipe_err ? a.pipe_err : pipe_error_word();
-    p.bounded = bounded ? 1 : 0;
-    if (bounded) {  // the board's rows in owned-row coordinates, clipped to the buffer (Script.fsx:6-13)
-        const int64_t lo = -a.y0 > -a.ghost ? -a.y0 : -a.ghost;
-        const int64_t hi = a.height - a.y0 < a.rows + a.ghost ? a.height - a.y0 : a.rows + a.ghost;
-        p.live_lo = (int32_t)lo;
-        p.live_hi = (int32_t)hi;
-    }
-    return p;
 }
 
 hipError_t launch_stream_step(const uint32_t* src, uint32_t* dst, StreamArgs a, int k, bool bounded, bool wrap,
@@ -1509,11 +1092,13 @@ hipError_t launch_stream_step(const uint32_t* src, uint32_t* dst, StreamArgs a, 
     }
     plan_stream(a, k, bounded, wrap);
     if (a.nsegs <= 0) return hipSuccess;
-#define GOL_LAUNCH(K_, M_) \
-    if (k == K_ && a.ilv == M_) return launch_km<K_, M_>(src, dst, a, bounded, wrap, s);
-    GOL_FOR_EACH_KM(GOL_LAUNCH)
-#undef GOL_LAUNCH
-    return hipErrorInvalidValue;
+    const Variant var = variant_for(k, a.ilv, bounded, wrap, stream_narrow(a.words, a.ilv, k, bounded, a.rag_bits));
+    if (!var.fn) return hipErrorInvalidValue;
+    const int64_t waves = (a.nstrips * a.nsegs + a.rem_units) * (a.split ? var.wpb / 4 : 1);
+    const unsigned blocks = (unsigned)((waves + var.wpb - 1) / var.wpb);
+    void* args[] = {&src, &dst, &a};
+    (void)hipLaunchKernel(var.fn, dim3(blocks), dim3(kWave * var.wpb), args, 0, s);
+    return hipGetLastError();
 }
 
 }  // namespace gol

@@ -6,7 +6,7 @@
 Prints one JSON object: the modelled SQ_INSTS_VALU per launch, split into what B3/S23 needs and each overhead the
 plan adds, next to the measured counter (profiles/r5/final/pmc_sq_*.json, device code c2ddb3d36af2fd90).
 
-deep: mirrors plan_stream (csrc/gol_step.hip) for one balanced round of `resident` waves (256 CUs x 12 waves at the
+deep: mirrors plan_stream (csrc/gol_stream_plan.cpp) for one balanced round of `resident` waves (256 CUs x 12 waves at the
 (12, 2) pass's 3 waves per SIMD): 16 seam strips of 63 blocks + 16 remainder blocks per 65536-cell row, 62 group
 segments of 1058 rows (the last 998), three waves per SIMD group splitting a segment by the split / split2 shares
 (group_cut), the remainder blocks packed 3 sub-strips per wave.  Per wave: ceil((share + 2K) / 4) trips of 4 rows;
