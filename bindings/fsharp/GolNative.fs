@@ -99,6 +99,16 @@ extern int gol_batch_synchronize(nativeint batch)
 // steps may be null
 [<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
 extern int gol_ensemble_cycles(nativeint batch, int64 maxGenerations, int64[] transient, int64[] period, int64[] population, int64[] steps, int64 n)
+// life-like rules (gol.h): two 9-bit masks, bit n = n live neighbours; parse / format are host-only; the batch's rule
+// (B3/S23 until set) is the rule of step, step_timed, step_trace and the census
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl, CharSet = CharSet.Ansi)>]
+extern int gol_rule_parse(string text, int& birth, int& survive)
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int gol_rule_format(int birth, int survive, byte[] out, int64 len)   // len >= 22
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int gol_ensemble_set_rule(nativeint batch, int birth, int survive)
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int gol_ensemble_rule(nativeint batch, int& birth, int& survive)
 [<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
 extern nativeint gol_last_error()
 
@@ -159,6 +169,12 @@ type Batch(width: int, height: int, count: int, boundary: Boundary) =
     member _.Count = count
     member _.Seed(seeds: int[], mode: InitMode) =
         check "gol_batch_seed_dotnet" (gol_batch_seed_dotnet(h, seeds, int64 seeds.Length, int mode))
+    /// "B36/S23", "S23/B36" or "23/36": the rule of every later Step / StepTrace (B3/S23 until set)
+    member _.SetRule(rule: string) =
+        let mutable birth = 0
+        let mutable survive = 0
+        check "gol_rule_parse" (gol_rule_parse(rule, &birth, &survive))
+        check "gol_ensemble_set_rule" (gol_ensemble_set_rule(h, birth, survive))
     member _.Step(generations: int64) = check "gol_batch_step" (gol_batch_step(h, generations))
     /// Steps and returns trace.[t * count + i] = population of board i after generation every * (t + 1) of this call.
     member _.StepTrace(generations: int64, every: int64) =

@@ -174,9 +174,15 @@ SIGNATURES = {
     "gol_batch_render_gray8": (ctypes.c_int, [vp, i64, u8p, i64, ctypes.c_uint8]),
     "gol_batch_synchronize": (ctypes.c_int, [vp]),
     "gol_ensemble_cycles": (ctypes.c_int, [vp, i64, i64p, i64p, i64p, i64p, i64]),
+    # life-like rules of a batch (two 9-bit masks: birth, survive)
+    "gol_rule_parse": (ctypes.c_int, [ctypes.c_char_p, ip, ip]),
+    "gol_rule_format": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_char_p, i64]),
+    "gol_ensemble_set_rule": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int]),
+    "gol_ensemble_rule": (ctypes.c_int, [vp, ip, ip]),
     # test and A/B knobs (csrc/gol_debug.h: internal, not part of the gol.h boundary)
     "gol_debug_batch_group_waves": (ctypes.c_int, [vp, ctypes.c_int]),
     "gol_debug_ensemble_cycles_us": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_double)]),
+    "gol_debug_batch_rule_table": (ctypes.c_int, [vp, ctypes.c_int]),
     "gol_debug_set_option": (ctypes.c_int, [vp, ctypes.c_char_p, i64]),
     "gol_debug_get_option": (ctypes.c_int, [vp, ctypes.c_char_p, i64p]),
     "gol_debug_option_names": (ctypes.c_char_p, []),
@@ -352,6 +358,22 @@ def batch_supported(width: int, height: int) -> int:
     """gol_batch_supported: rows per lane (1..4) of a width x height board in a BoardBatch, 0 when a batch does not
     take the geometry.  Host-only."""
     return int(load().gol_batch_supported(width, height))
+
+
+def rule_parse(text: str) -> tuple:
+    """gol_rule_parse: ``(birth, survive)``, the two 9-bit masks of "B36/S23", "S23/B36" or "23/36" (any letter case,
+    blanks around); ValueError for anything else.  Host-only."""
+    b, s = ctypes.c_int(), ctypes.c_int()
+    raw = text.encode() if isinstance(text, str) else text
+    check(load().gol_rule_parse(raw, ctypes.byref(b), ctypes.byref(s)), "gol_rule_parse")
+    return b.value, s.value
+
+
+def rule_format(birth: int, survive: int) -> str:
+    """gol_rule_format: the canonical "B<ascending digits>/S<ascending digits>" of two masks in 0..0x1FF.  Host-only."""
+    buf = ctypes.create_string_buffer(22)
+    check(load().gol_rule_format(birth, survive, buf, len(buf)), "gol_rule_format")
+    return buf.value.decode()
 
 
 def exchange_plan(height: int, boundary: int, nparts: int, ghost: int, k: int) -> list:

@@ -9,7 +9,8 @@ population curves, extinction times and soup censuses over thousands of seeds ar
 other question asked of an ensemble of soups -- after how many generations does each board settle, and into a cycle of
 what period -- in one launch too: each wave runs the cycle search on the board in its registers
 (``csrc/gol_cycles.hip``), where ``step(1)`` + ``hashes()`` per generation would be thousands of launches
-and readbacks.
+and readbacks.  All of it runs under the batch's rule: B3/S23 unless ``rule=`` / ``set_rule`` names another life-like
+rule ("B36/S23", "B3678/S34678", ...).
 """
 from __future__ import annotations
 
@@ -32,16 +33,21 @@ class BoardBatch:
 
     The geometry is the single-wave pass's: 3 <= width <= 128 and ``batch_supported(width, height) > 0`` (1 to 4 rows
     per lane on at most 64 lanes); anything else raises NotImplementedError.  boundary: ``TORUS`` or ``BOUNDED``.
-    Cell arrays are ``(n, height, width)`` uint8, nonzero = alive.
+    Cell arrays are ``(n, height, width)`` uint8, nonzero = alive.  rule: a life-like rule as ``set_rule`` takes it.
     """
 
-    def __init__(self, width: int, height: int, count: int, boundary: int = TORUS):
+    def __init__(self, width: int, height: int, count: int, boundary: int = TORUS, rule="B3/S23"):
         self._lib = _lib.load()
         h = ctypes.c_void_p()
         check(self._lib.gol_batch_create(width, height, boundary, count, ctypes.byref(h)), "gol_batch_create")
         self._h = h
         _lib.hold(self)
         self.width, self.height, self.count, self.boundary = width, height, count, boundary
+        try:
+            self.set_rule(rule)
+        except Exception:
+            self.close()
+            raise
 
     # ---------------------------------------------------------------- lifetime
     def close(self) -> None:
@@ -108,6 +114,23 @@ class BoardBatch:
         check(self._lib.gol_batch_clear(self._h), "gol_batch_clear")
         return self
 
+    # ---------------------------------------------------------------- rule
+    def set_rule(self, rule) -> "BoardBatch":
+        """The rule of every later ``step``, ``step_timed``, ``step_trace`` and ``cycles``: a string ("B36/S23",
+        "S23/B36" or "23/36") or a ``(birth, survive)`` pair of 9-bit masks (bit n: n live neighbours).  Cells, the
+        generation counter, populations and hashes are untouched, and ``set_cells``, the seeds and ``clear`` keep the
+        rule.  On a bounded board the cells outside stay dead under any rule, B0 included."""
+        birth, survive = _lib.rule_parse(rule) if isinstance(rule, (str, bytes)) else rule
+        check(self._lib.gol_ensemble_set_rule(self._h, int(birth), int(survive)), "gol_ensemble_set_rule")
+        return self
+
+    @property
+    def rule(self) -> str:
+        """The batch's rule in canonical form, "B3/S23" for a new batch."""
+        b, s = ctypes.c_int(), ctypes.c_int()
+        check(self._lib.gol_ensemble_rule(self._h, ctypes.byref(b), ctypes.byref(s)), "gol_ensemble_rule")
+        return _lib.rule_format(b.value, s.value)
+
     # ---------------------------------------------------------------- stepping
     def step(self, generations: int = 1) -> "BoardBatch":
         check(self._lib.gol_batch_step(self._h, generations), "gol_batch_step")
@@ -156,13 +179,14 @@ class BoardBatch:
         (1 .. 2**20): ``(transient, period, population)``, each a (count,) int64 array, and ``steps`` as a fourth when
         ``with_steps``.
 
-        For board i let B_0 be its current cells and B_{t+1} the next B3/S23 generation of B_t under the batch's
-        boundary, t* the smallest t >= 1 with B_t == B_s for some s < t, mu = s (the transient) and lambda = t* - mu
-        (the period, minimal by construction).  Resolved, exactly when t* = mu + lambda <= max_generations:
+        For board i let B_0 be its current cells and B_{t+1} the next generation of B_t under the batch's rule and
+        boundary, t* the smallest t >= 1 with B_t == B_s for some s < t, mu = s (the transient) and lambda = t* - mu (the
+        period, minimal by construction).  Resolved, exactly when t* = mu + lambda <= max_generations:
         ``transient[i] = mu``, ``period[i] = lambda``, ``population[i]`` = live cells of B_mu.  Unresolved, exactly when
         t* > max_generations: ``(-1, 0, 0)``.  The answer depends on the board and ``max_generations`` only, never on
-        how the search went.  Cells are compared in place: a glider on a 100 x 100 torus is ``(0, 400, 5)``, a still
-        life ``(0, 1, population)``, an empty board ``(0, 1, 0)``.
+        how the search went.  Cells are compared in place: under B3/S23 a glider on a 100 x 100 torus is
+        ``(0, 400, 5)``, a still life ``(0, 1, population)``, an empty board ``(0, 1, 0)`` (under ``B0/S`` it is
+        ``(0, 2, 0)``).
 
         Read-only: cells, hashes and ``generation`` are unchanged.  ``steps[i]`` is the number of generation steps the
         wave ran for board i -- cost accounting, not a property of the board, free to change between versions, never

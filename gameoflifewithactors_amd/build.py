@@ -26,6 +26,7 @@ HEADERS = [
     os.path.join(CSRC, "gol_wave_body.h"),
     os.path.join(CSRC, "gol_batch_host.h"),
     os.path.join(CSRC, "gol_cycle_search.h"),
+    os.path.join(CSRC, "gol_rule.h"),
     os.path.join(ROOT, "include", "gol", "gol.h"),
 ]
 ARCH = "gfx950"

@@ -11,6 +11,7 @@
 #include "gol_board.h"
 #include "gol_cycle_search.h"
 #include "gol_debug.h"
+#include "gol_rule.h"
 
 using gol::DeviceBuffer;
 using gol::DeviceGuard;
@@ -27,6 +28,8 @@ struct gol_batch {
     uint32_t* words = nullptr;  // count * H * nw
     int32_t* cycles = nullptr;  // count * 4 result words of gol_ensemble_cycles, allocated by its first call
     int64_t generation = 0;
+    uint32_t rule = gol::kRuleLifePacked;  // birth | survive << 9 (gol_ensemble_set_rule)
+    bool rule_table = false;  // B3/S23 through the rule-table kernels too (gol_debug_batch_rule_table)
     double cycles_us = -1;  // device time of the last census launch (gol_debug_ensemble_cycles_us)
 
     int64_t cells() const { return W * H; }
@@ -222,7 +225,7 @@ int gol_batch_step(gol_batch* b, int64_t generations) {
         if (generations < 0) return fail(GOL_ERR_INVALID, "generations must be >= 0");
         if (generations == 0) return GOL_OK;
         GOL_HIP(gol::launch_batch_step(b->words, b->count, b->W, b->H, b->boundary == GOL_BOUNDED, 1, generations,
-                                       nullptr, b->group_waves, b->stream));
+                                       nullptr, b->group_waves, b->rule, b->rule_table, b->stream));
         b->generation += generations;
         return GOL_OK;
     });
@@ -237,7 +240,7 @@ int gol_batch_step_timed(gol_batch* b, int64_t generations, double* elapsed_us) 
         GOL_HIP(hipEventRecord(ev.e0, b->stream));
         if (generations > 0)
             GOL_HIP(gol::launch_batch_step(b->words, b->count, b->W, b->H, b->boundary == GOL_BOUNDED, 1, generations,
-                                           nullptr, b->group_waves, b->stream));
+                                           nullptr, b->group_waves, b->rule, b->rule_table, b->stream));
         GOL_HIP(hipEventRecord(ev.e1, b->stream));
         b->generation += generations;
         return ev.elapsed_us(elapsed_us);
@@ -255,7 +258,7 @@ int gol_batch_step_trace(gol_batch* b, int64_t generations, int64_t every, uint3
         const size_t bytes = (size_t)len * sizeof(uint32_t);
         GOL_RC(dev.alloc(bytes, "trace"));
         GOL_HIP(gol::launch_batch_step(b->words, b->count, b->W, b->H, b->boundary == GOL_BOUNDED, samples, every,
-                                       dev.as<uint32_t>(), b->group_waves, b->stream));
+                                       dev.as<uint32_t>(), b->group_waves, b->rule, b->rule_table, b->stream));
         b->generation += generations;
         GOL_HIP(hipMemcpyAsync(trace, dev.p, bytes, hipMemcpyDeviceToHost, b->stream));
         GOL_HIP(hipStreamSynchronize(b->stream));
@@ -327,7 +330,7 @@ int gol_ensemble_cycles(gol_batch* b, int64_t max_generations, int64_t* transien
         GOL_RC(ev.create());
         GOL_HIP(hipEventRecord(ev.e0, b->stream));
         GOL_HIP(gol::launch_batch_cycles(b->words, b->count, b->W, b->H, b->boundary == GOL_BOUNDED, max_generations,
-                                         b->cycles, b->stream));
+                                         b->cycles, b->rule, b->rule_table, b->stream));
         GOL_HIP(hipEventRecord(ev.e1, b->stream));
         GOL_HIP(hipMemcpyAsync(host.data(), b->cycles, bytes, hipMemcpyDeviceToHost, b->stream));
         GOL_HIP(hipStreamSynchronize(b->stream));
@@ -343,6 +346,33 @@ int gol_ensemble_cycles(gol_batch* b, int64_t max_generations, int64_t* transien
     });
 }
 
+int gol_rule_parse(const char* text, int* birth, int* survive) {
+    const char* why = "";
+    return gol::rule_parse(text, birth, survive, &why) ? GOL_OK : fail(GOL_ERR_INVALID, std::string("rule: ") + why);
+}
+
+int gol_rule_format(int birth, int survive, char* out, int64_t len) {
+    const char* why = "";
+    return gol::rule_format(birth, survive, out, len, &why) ? GOL_OK : fail(GOL_ERR_INVALID, std::string("rule: ") + why);
+}
+
+int gol_ensemble_set_rule(gol_batch* b, int birth, int survive) {
+    return with_batch(b, [&] {
+        if (!gol::rule_masks_ok(birth, survive))
+            return fail(GOL_ERR_INVALID, "birth and survive masks must lie in 0..0x1FF");
+        b->rule = gol::rule_pack(birth, survive);
+        return GOL_OK;
+    });
+}
+
+int gol_ensemble_rule(gol_batch* b, int* birth, int* survive) {
+    if (!b) return fail(GOL_ERR_INVALID, "null batch");
+    std::lock_guard<std::mutex> g(b->mu);
+    if (birth) *birth = (int)(b->rule & gol::kRuleMaskMax);
+    if (survive) *survive = (int)(b->rule >> 9);
+    return GOL_OK;
+}
+
 int gol_batch_synchronize(gol_batch* b) {
     return with_batch(b, [&] {
         GOL_HIP(hipStreamSynchronize(b->stream));
@@ -354,6 +384,14 @@ int gol_debug_batch_group_waves(gol_batch* b, int waves) {
     return with_batch(b, [&] {
         if (waves != 1 && waves != 4) return fail(GOL_ERR_INVALID, "waves per workgroup must be 1 or 4");
         b->group_waves = waves;
+        return GOL_OK;
+    });
+}
+
+int gol_debug_batch_rule_table(gol_batch* b, int force) {
+    return with_batch(b, [&] {
+        if (force != 0 && force != 1) return fail(GOL_ERR_INVALID, "force must be 0 or 1");
+        b->rule_table = force == 1;
         return GOL_OK;
     });
 }

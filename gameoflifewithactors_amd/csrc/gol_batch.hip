@@ -12,6 +12,7 @@
 // most 64 lanes).
 #include "gol_batch_host.h"
 #include "gol_internal.h"
+#include "gol_rule.h"
 #include "gol_wave_body.h"
 
 namespace gol {
@@ -20,9 +21,15 @@ namespace {
 // Board `blockIdx.x * waves per group + wave` runs `samples` x `every` generations.  TRACE: after each `every`
 // generations the board's population goes to trace[t * count + board] (t = 0 .. samples - 1); otherwise samples is 1
 // and trace unused.  A wave past the last board leaves before it touches memory.
-template <int NW, int RPL, bool BOUNDED, bool TRACE>
+//
+// PackedRule is empty or one uint32_t.  Empty: B3/S23 by life_next, the kernel and its arguments as they were before
+// rules existed.  One word: any life-like rule by its packed masks (gol_wave_body.h wave_rule).  launch_batch_step
+// picks the family; nothing else lets a rule change what runs.
+template <int NW, int RPL, bool BOUNDED, bool TRACE, class... PackedRule>
 __global__ __launch_bounds__(256) void gol_batch_step(uint32_t* __restrict__ words, int64_t count, int W, int H,
-                                                      int samples, int64_t every, uint32_t* __restrict__ trace) {
+                                                      int samples, int64_t every, uint32_t* __restrict__ trace,
+                                                      PackedRule... packed_rule) {
+    const auto rule = wave_rule(packed_rule...);
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t board = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave;
@@ -44,7 +51,7 @@ __global__ __launch_bounds__(256) void gol_batch_step(uint32_t* __restrict__ wor
     const WaveGeom geom = wave_geom<BOUNDED>(W, nl, lane);
 
     for (int t = 0; t < samples; t++) {
-        for (int64_t g = 0; g < every; g++) wave_generation<NW, RPL, BOUNDED>(w, geom);
+        for (int64_t g = 0; g < every; g++) wave_generation<NW, RPL, BOUNDED>(w, geom, rule);
         if (TRACE) {
             // lanes past the last active one hold whatever the arithmetic left there: they count as 0
             uint32_t pop = 0;
@@ -150,20 +157,27 @@ unsigned blocks(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
 template <int NW, int RPL>
 hipError_t step_nr(uint32_t* words, int64_t count, int W, int H, bool bounded, int samples, int64_t every,
-                   uint32_t* trace, int group_waves, hipStream_t s) {
+                   uint32_t* trace, int group_waves, bool table, uint32_t rule, hipStream_t s) {
     const dim3 grid(blocks(count, group_waves)), block(64 * group_waves);
-#define GOL_BATCH_LAUNCH(B, T) \
-    hipLaunchKernelGGL((gol_batch_step<NW, RPL, B, T>), grid, block, 0, s, words, count, W, H, samples, every, trace)
+#define GOL_BATCH_LAUNCH(B, T)                                                                                        \
+    if (table)                                                                                                        \
+        hipLaunchKernelGGL((gol_batch_step<NW, RPL, B, T, uint32_t>), grid, block, 0, s, words, count, W, H, samples,      \
+                           every, trace, rule);                                                                       \
+    else                                                                                                              \
+        hipLaunchKernelGGL((gol_batch_step<NW, RPL, B, T>), grid, block, 0, s, words, count, W, H, samples, every,    \
+                           trace)
     if (bounded) {
-        if (trace)
+        if (trace) {
             GOL_BATCH_LAUNCH(true, true);
-        else
+        } else {
             GOL_BATCH_LAUNCH(true, false);
+        }
     } else {
-        if (trace)
+        if (trace) {
             GOL_BATCH_LAUNCH(false, true);
-        else
+        } else {
             GOL_BATCH_LAUNCH(false, false);
+        }
     }
 #undef GOL_BATCH_LAUNCH
     return hipGetLastError();
@@ -171,12 +185,16 @@ hipError_t step_nr(uint32_t* words, int64_t count, int W, int H, bool bounded, i
 
 template <int NW>
 hipError_t step_n(uint32_t* words, int64_t count, int W, int H, bool bounded, int samples, int64_t every,
-                  uint32_t* trace, int group_waves, int rpl, hipStream_t s) {
+                  uint32_t* trace, int group_waves, int rpl, bool table, uint32_t rule, hipStream_t s) {
     switch (rpl) {
-        case 1: return step_nr<NW, 1>(words, count, W, H, bounded, samples, every, trace, group_waves, s);
-        case 2: return step_nr<NW, 2>(words, count, W, H, bounded, samples, every, trace, group_waves, s);
-        case 3: return step_nr<NW, 3>(words, count, W, H, bounded, samples, every, trace, group_waves, s);
-        case 4: return step_nr<NW, 4>(words, count, W, H, bounded, samples, every, trace, group_waves, s);
+        case 1: return step_nr<NW, 1>(words, count, W, H, bounded, samples, every, trace, group_waves, table, rule,
+                                          s);
+        case 2: return step_nr<NW, 2>(words, count, W, H, bounded, samples, every, trace, group_waves, table, rule,
+                                          s);
+        case 3: return step_nr<NW, 3>(words, count, W, H, bounded, samples, every, trace, group_waves, table, rule,
+                                          s);
+        case 4: return step_nr<NW, 4>(words, count, W, H, bounded, samples, every, trace, group_waves, table, rule,
+                                          s);
     }
     return hipErrorInvalidValue;
 }
@@ -184,16 +202,26 @@ hipError_t step_n(uint32_t* words, int64_t count, int W, int H, bool bounded, in
 }  // namespace
 
 hipError_t launch_batch_step(uint32_t* words, int64_t count, int64_t W, int64_t H, bool bounded, int64_t samples,
-                             int64_t every, uint32_t* trace, int group_waves, hipStream_t s) {
+                             int64_t every, uint32_t* trace, int group_waves, uint32_t rule, bool force_table,
+                             hipStream_t s) {
     const int rpl = wave_resident_rpl(W, H);
-    if (!rpl || count < 1 || count > kBatchCountMax || samples < 1 || samples > INT32_MAX || every < 1 ||
+    const bool table = force_table || rule != kRuleLifePacked;  // B3/S23 runs the code it always ran
+    if (!rpl || rule >= (1u << 18) || count < 1 || count > kBatchCountMax || samples < 1 || samples > INT32_MAX || every < 1 ||
         (!trace && samples != 1) || (group_waves != 1 && group_waves != 4))
         return hipErrorInvalidValue;
     switch ((int)((W + 31) / 32)) {
-        case 1: return step_n<1>(words, count, (int)W, (int)H, bounded, (int)samples, every, trace, group_waves, rpl, s);
-        case 2: return step_n<2>(words, count, (int)W, (int)H, bounded, (int)samples, every, trace, group_waves, rpl, s);
-        case 3: return step_n<3>(words, count, (int)W, (int)H, bounded, (int)samples, every, trace, group_waves, rpl, s);
-        case 4: return step_n<4>(words, count, (int)W, (int)H, bounded, (int)samples, every, trace, group_waves, rpl, s);
+        case 1:
+            return step_n<1>(words, count, (int)W, (int)H, bounded, (int)samples, every, trace, group_waves, rpl, table,
+                             rule, s);
+        case 2:
+            return step_n<2>(words, count, (int)W, (int)H, bounded, (int)samples, every, trace, group_waves, rpl, table,
+                             rule, s);
+        case 3:
+            return step_n<3>(words, count, (int)W, (int)H, bounded, (int)samples, every, trace, group_waves, rpl, table,
+                             rule, s);
+        case 4:
+            return step_n<4>(words, count, (int)W, (int)H, bounded, (int)samples, every, trace, group_waves, rpl, table,
+                             rule, s);
     }
     return hipErrorInvalidValue;
 }

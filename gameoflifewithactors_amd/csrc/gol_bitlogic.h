@@ -1,4 +1,5 @@
-// gol_bitlogic.h -- bit-sliced B3/S23 for 32 cells per 32-bit word (host + gfx950 device).
+// gol_bitlogic.h -- bit-sliced B3/S23 for 32 cells per 32-bit word (host + gfx950 device), and at the end of the file
+// the same for any life-like rule given as two masks (rule_next_row; the batch handle's rules).
 //
 // Replaces, for 32 cells at once, the per-cell neighbour gather and rule of the reference actor:
 //   GameOfLife/GameOfLife/GameOfLifeLogic.fs:56-63  (Akka: GameOfLifeAkka/GameofLife.fs:105-112)
@@ -83,6 +84,92 @@ GOL_HD uint32_t life_next(uint32_t sP, uint32_t cP, uint32_t sC, uint32_t cC, ui
     const uint32_t o1 = lut3<0x27>(A, Y, alive);
     const uint32_t o2 = lut3<0x19>(B, X, Y);
     return lut3<0x24>(o1, o2, A);
+}
+
+// ---- any life-like rule (gol_rule.h: birth | survive << 9, uniform over a launch) on N words of one row at a time.
+//
+// t = A + 2 (B + X) + 4 Y is the 9-cell total, 0..9, as four bit planes: t0 = A, t1 = B ^ X, t2 = Y ^ (B & X),
+// t3 = Y & B & X.  A dead cell with n neighbours has t = n, a live one t = n + 1, so
+//   next = OR over set birth bits n of (t == n & ~alive)  |  OR over set survive bits n of (t == n + 1 & alive).
+// For t <= 7 a term is a minterm of (t0, t1, t2) -- one LUT with a compile-time immediate -- under a qualifier word
+// (~t3 & ~alive or ~t3 & alive, made once), ORed in by one a | (b & c).  t >= 8 leaves t1 = t2 = 0, so birth 8 is
+// t3 & ~t0 & ~alive, survive 7 is t3 & ~t0 & alive and survive 8 is t3 & t0 & alive: one LUT and one OR each.  Every
+// term sits under a test of its rule bit -- a scalar branch on the device, taken once for the N words -- so a clear bit
+// costs no vector instruction: 9 fixed and 2 per set bit, per word.
+//
+// SURVIVE only names the planes in the other order (t2, t1, t0: the minterm of V is then bit rev3(V) of the LUT).  Birth
+// n + 1 and survive n test the same t, and given one spelling of that minterm the compiler computes it ahead of both
+// branches, for all seven t and whatever the rule: 7 instructions per word that a rule of three or four digits never
+// needs.
+template <unsigned V, bool SURVIVE, int N>
+GOL_HD void rule_term(uint32_t (&acc)[N], const uint32_t (&t0)[N], const uint32_t (&t1)[N], const uint32_t (&t2)[N],
+                      const uint32_t (&q)[N]) {
+    constexpr unsigned R = (V & 1u) << 2 | (V & 2u) | (V & 4u) >> 2;
+#pragma unroll
+    for (int j = 0; j < N; j++) {
+        const uint32_t m = SURVIVE ? lut3<(1u << R)>(t2[j], t1[j], t0[j]) : lut3<(1u << V)>(t0[j], t1[j], t2[j]);
+        acc[j] = lut3<0xEA>(acc[j], m, q[j]);
+    }
+}
+template <unsigned L, int N>
+GOL_HD void rule_term_high(uint32_t (&acc)[N], const uint32_t (&t3)[N], const uint32_t (&t0)[N],
+                           const uint32_t (&alive)[N]) {
+#pragma unroll
+    for (int j = 0; j < N; j++) acc[j] |= lut3<L>(t3[j], t0[j], alive[j]);
+}
+
+template <int N>
+GOL_HD void rule_next_row(const uint32_t (&sP)[N], const uint32_t (&cP)[N], const uint32_t (&sC)[N],
+                          const uint32_t (&cC)[N], const uint32_t (&sN)[N], const uint32_t (&cN)[N],
+                          const uint32_t (&alive)[N], uint32_t rule, uint32_t (&out)[N]) {
+    uint32_t t0[N], t1[N], t2[N], t3[N], qd[N], qa[N], acc[N];
+#pragma unroll
+    for (int j = 0; j < N; j++) {
+        const uint32_t B = lut3<0xE8>(sP[j], sC[j], sN[j]);
+        const uint32_t X = lut3<0x96>(cP[j], cC[j], cN[j]);
+        const uint32_t Y = lut3<0xE8>(cP[j], cC[j], cN[j]);
+        t0[j] = lut3<0x96>(sP[j], sC[j], sN[j]);
+        t1[j] = B ^ X;
+        t2[j] = lut3<0x78>(B, X, Y);  // (a & b) ^ c
+        t3[j] = lut3<0x80>(B, X, Y);  // a & b & c
+        qd[j] = ~(t3[j] | alive[j]);
+        qa[j] = alive[j] & ~t3[j];
+        acc[j] = 0;
+    }
+#if defined(__HIP_DEVICE_COMPILE__)
+    // The rule stays one scalar register tested here bit by bit (s_bitcmp1_b32, s_cbranch_scc): hoisted out of the
+    // generation loop the 18 tests become 18 lane masks in register pairs, re-tested by vector compares.
+    asm volatile("" : "+s"(rule));
+#endif
+    if (rule >> 0 & 1) rule_term<0, false>(acc, t0, t1, t2, qd);  // birth n: t == n, dead
+    if (rule >> 1 & 1) rule_term<1, false>(acc, t0, t1, t2, qd);
+    if (rule >> 2 & 1) rule_term<2, false>(acc, t0, t1, t2, qd);
+    if (rule >> 3 & 1) rule_term<3, false>(acc, t0, t1, t2, qd);
+    if (rule >> 4 & 1) rule_term<4, false>(acc, t0, t1, t2, qd);
+    if (rule >> 5 & 1) rule_term<5, false>(acc, t0, t1, t2, qd);
+    if (rule >> 6 & 1) rule_term<6, false>(acc, t0, t1, t2, qd);
+    if (rule >> 7 & 1) rule_term<7, false>(acc, t0, t1, t2, qd);
+    if (rule >> 8 & 1) rule_term_high<0x02>(acc, t3, t0, alive);  // t == 8, dead: a & ~b & ~c
+    if (rule >> 9 & 1) rule_term<1, true>(acc, t0, t1, t2, qa);  // survive n: t == n + 1, alive
+    if (rule >> 10 & 1) rule_term<2, true>(acc, t0, t1, t2, qa);
+    if (rule >> 11 & 1) rule_term<3, true>(acc, t0, t1, t2, qa);
+    if (rule >> 12 & 1) rule_term<4, true>(acc, t0, t1, t2, qa);
+    if (rule >> 13 & 1) rule_term<5, true>(acc, t0, t1, t2, qa);
+    if (rule >> 14 & 1) rule_term<6, true>(acc, t0, t1, t2, qa);
+    if (rule >> 15 & 1) rule_term<7, true>(acc, t0, t1, t2, qa);
+    if (rule >> 16 & 1) rule_term_high<0x20>(acc, t3, t0, alive);  // t == 8, alive: a & ~b & c
+    if (rule >> 17 & 1) rule_term_high<0x80>(acc, t3, t0, alive);  // t == 9, alive: a & b & c
+#pragma unroll
+    for (int j = 0; j < N; j++) out[j] = acc[j];
+}
+
+// The same seven inputs as life_next, 32 cells.
+GOL_HD uint32_t rule_next(uint32_t sP, uint32_t cP, uint32_t sC, uint32_t cC, uint32_t sN, uint32_t cN, uint32_t alive,
+                          uint32_t rule) {
+    const uint32_t a[7][1] = {{sP}, {cP}, {sC}, {cC}, {sN}, {cN}, {alive}};
+    uint32_t out[1];
+    rule_next_row<1>(a[0], a[1], a[2], a[3], a[4], a[5], a[6], rule, out);
+    return out[0];
 }
 
 }  // namespace gol

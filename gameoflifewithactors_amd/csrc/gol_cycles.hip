@@ -11,23 +11,26 @@
 #include "gol_batch_host.h"
 #include "gol_cycle_search.h"
 #include "gol_internal.h"
+#include "gol_rule.h"
 #include "gol_wave_body.h"
 
 namespace gol {
 namespace {
 
+template <class Rule>
 struct CycleWave {
     WaveGeom geom;
+    Rule rule;  // gol_wave_body.h RuleLife / RuleTable
     uint64_t lanes;  // the lanes that hold rows of the board: what the others hold never counts as a difference
 };
 
 // One board in the wave's registers, as the search's state type.
-template <int NW, int RPL, bool BOUNDED>
+template <int NW, int RPL, bool BOUNDED, class Rule>
 struct WaveBoard {
     uint32_t w[RPL][NW];
-    const CycleWave* wave;
+    const CycleWave<Rule>* wave;
 
-    __device__ __forceinline__ void step() { wave_generation<NW, RPL, BOUNDED>(w, wave->geom); }
+    __device__ __forceinline__ void step() { wave_generation<NW, RPL, BOUNDED>(w, wave->geom, wave->rule); }
     // the same value in every lane: each lane ORs the XOR of its words (one v_bitop3 per word), one ballot
     __device__ __forceinline__ bool equal(const WaveBoard& o) const {
         uint32_t d = 0;
@@ -40,19 +43,24 @@ struct WaveBoard {
 };
 
 // Board blockIdx.x: out[4 board ..] = transient, period, population of B_transient, generation steps run.
-template <int NW, int RPL, bool BOUNDED>
+// PackedRule is empty (B3/S23 by life_next: the kernel as it was before rules existed) or one uint32_t (any life-like
+// rule by its packed masks), as in gol_batch.hip: launch_batch_cycles picks.
+template <int NW, int RPL, bool BOUNDED, class... PackedRule>
 __global__ __launch_bounds__(64) void gol_batch_cycles(const uint32_t* __restrict__ words, int64_t count, int W, int H,
-                                                       int max_generations, int32_t* __restrict__ out) {
+                                                       int max_generations, int32_t* __restrict__ out,
+                                                       PackedRule... packed_rule) {
+    using Rule = decltype(wave_rule(packed_rule...));
     const int lane = threadIdx.x;
     const int64_t board = blockIdx.x;
     if (board >= count) return;
     const int nl = H / RPL;  // active lanes
     const bool active = lane < nl;
     const uint32_t* rows = words + (board * H + lane * RPL) * NW;  // this lane's RPL * NW words
-    CycleWave cw;
+    CycleWave<Rule> cw;
     cw.geom = wave_geom<BOUNDED>(W, nl, lane);
+    cw.rule = wave_rule(packed_rule...);
     cw.lanes = __ballot(active);
-    using Board = WaveBoard<NW, RPL, BOUNDED>;
+    using Board = WaveBoard<NW, RPL, BOUNDED, Rule>;
     const auto load = [&]() {
         Board b;
         b.wave = &cw;
@@ -87,10 +95,17 @@ __global__ __launch_bounds__(64) void gol_batch_cycles(const uint32_t* __restric
 }
 
 template <int NW, int RPL>
-hipError_t cycles_nr(const uint32_t* words, int64_t count, int W, int H, bool bounded, int G, int32_t* out,
-                     hipStream_t s) {
+hipError_t cycles_nr(const uint32_t* words, int64_t count, int W, int H, bool bounded, int G, int32_t* out, bool table,
+                     uint32_t rule, hipStream_t s) {
     const dim3 grid((unsigned)count), block(64);  // count <= 2^22
-    if (bounded)
+    if (table) {
+        if (bounded)
+            hipLaunchKernelGGL((gol_batch_cycles<NW, RPL, true, uint32_t>), grid, block, 0, s, words, count, W, H, G, out,
+                               rule);
+        else
+            hipLaunchKernelGGL((gol_batch_cycles<NW, RPL, false, uint32_t>), grid, block, 0, s, words, count, W, H, G, out,
+                               rule);
+    } else if (bounded)
         hipLaunchKernelGGL((gol_batch_cycles<NW, RPL, true>), grid, block, 0, s, words, count, W, H, G, out);
     else
         hipLaunchKernelGGL((gol_batch_cycles<NW, RPL, false>), grid, block, 0, s, words, count, W, H, G, out);
@@ -99,12 +114,12 @@ hipError_t cycles_nr(const uint32_t* words, int64_t count, int W, int H, bool bo
 
 template <int NW>
 hipError_t cycles_n(const uint32_t* words, int64_t count, int W, int H, bool bounded, int G, int32_t* out, int rpl,
-                    hipStream_t s) {
+                    bool table, uint32_t rule, hipStream_t s) {
     switch (rpl) {
-        case 1: return cycles_nr<NW, 1>(words, count, W, H, bounded, G, out, s);
-        case 2: return cycles_nr<NW, 2>(words, count, W, H, bounded, G, out, s);
-        case 3: return cycles_nr<NW, 3>(words, count, W, H, bounded, G, out, s);
-        case 4: return cycles_nr<NW, 4>(words, count, W, H, bounded, G, out, s);
+        case 1: return cycles_nr<NW, 1>(words, count, W, H, bounded, G, out, table, rule, s);
+        case 2: return cycles_nr<NW, 2>(words, count, W, H, bounded, G, out, table, rule, s);
+        case 3: return cycles_nr<NW, 3>(words, count, W, H, bounded, G, out, table, rule, s);
+        case 4: return cycles_nr<NW, 4>(words, count, W, H, bounded, G, out, table, rule, s);
     }
     return hipErrorInvalidValue;
 }
@@ -112,17 +127,19 @@ hipError_t cycles_n(const uint32_t* words, int64_t count, int W, int H, bool bou
 }  // namespace
 
 hipError_t launch_batch_cycles(const uint32_t* words, int64_t count, int64_t W, int64_t H, bool bounded,
-                               int64_t max_generations, int32_t* out, hipStream_t s) {
+                               int64_t max_generations, int32_t* out, uint32_t rule, bool force_table,
+                               hipStream_t s) {
     const int rpl = wave_resident_rpl(W, H);
-    if (!rpl || !words || !out || count < 1 || count > kBatchCountMax || max_generations < 1 ||
+    const bool table = force_table || rule != kRuleLifePacked;  // B3/S23 runs the code it always ran
+    if (!rpl || rule >= (1u << 18) || !words || !out || count < 1 || count > kBatchCountMax || max_generations < 1 ||
         max_generations > kCycleGenerationsMax)
         return hipErrorInvalidValue;
     const int G = (int)max_generations;
     switch ((int)((W + 31) / 32)) {
-        case 1: return cycles_n<1>(words, count, (int)W, (int)H, bounded, G, out, rpl, s);
-        case 2: return cycles_n<2>(words, count, (int)W, (int)H, bounded, G, out, rpl, s);
-        case 3: return cycles_n<3>(words, count, (int)W, (int)H, bounded, G, out, rpl, s);
-        case 4: return cycles_n<4>(words, count, (int)W, (int)H, bounded, G, out, rpl, s);
+        case 1: return cycles_n<1>(words, count, (int)W, (int)H, bounded, G, out, rpl, table, rule, s);
+        case 2: return cycles_n<2>(words, count, (int)W, (int)H, bounded, G, out, rpl, table, rule, s);
+        case 3: return cycles_n<3>(words, count, (int)W, (int)H, bounded, G, out, rpl, table, rule, s);
+        case 4: return cycles_n<4>(words, count, (int)W, (int)H, bounded, G, out, rpl, table, rule, s);
     }
     return hipErrorInvalidValue;
 }

@@ -42,6 +42,10 @@ int gol_debug_pipe_errors(int* out);
 /* Batch handle (gol_batch.hip): boards (wavefronts) per workgroup of its step launches, 1 (the default) or 4 -- the
  * workgroup-shape A/B of DESIGN.md 4.9.  Results are identical. */
 int gol_debug_batch_group_waves(gol_batch* b, int waves);
+/* Batch handle: with force = 1 a B3/S23 batch runs the rule-table kernels too (any other rule always does; 0, the
+ * default, leaves B3/S23 on the life_next kernels).  Results are identical: the knob is what lets the table arithmetic
+ * be checked against life_next on the same boards, and timed against it. */
+int gol_debug_batch_rule_table(gol_batch* b, int force);
 /* Device time of the handle's last successful gol_ensemble_cycles launch, between two HIP events on its stream around
  * the kernel alone (the copy of the results is outside them); GOL_ERR_INVALID before the first such call. */
 int gol_debug_ensemble_cycles_us(gol_batch* b, double* elapsed_us);

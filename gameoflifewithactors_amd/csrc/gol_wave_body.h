@@ -12,6 +12,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "gol_bitlogic.h"
 
 namespace gol {
@@ -67,9 +69,22 @@ __device__ __forceinline__ WaveGeom wave_geom(int W, int nl, int lane) {
     return g;
 }
 
-// One synchronous B3/S23 generation of the wave's board, in place in w.
-template <int NW, int RPL, bool BOUNDED>
-__device__ __forceinline__ void wave_generation(uint32_t (&w)[RPL][NW], const WaveGeom& g) {
+// The rule of a generation, as a policy of wave_generation.  RuleLife is B3/S23 by life_next's LUT tree (the code every
+// pass had before rules existed); RuleTable is any life-like rule, its packed masks (gol_rule.h rule_pack: a kernel
+// argument, so uniform over the launch) evaluated by rule_next_row.
+struct RuleLife {};
+struct RuleTable {
+    uint32_t packed;
+};
+// The policy of a kernel whose trailing arguments are nothing (B3/S23) or the packed rule.
+__device__ __forceinline__ RuleLife wave_rule() { return RuleLife(); }
+__device__ __forceinline__ RuleTable wave_rule(uint32_t packed) { return RuleTable{packed}; }
+
+// One synchronous generation of the wave's board, in place in w.  Whatever the rule gives birth on: a row outside a
+// bounded board contributes zero sums (up_mask / dn_mask) and is no cell of the board, the last word is cut to the
+// row's cells (lastmask) before it is stored in w, and what lanes at or beyond nl hold is never read by an active lane.
+template <int NW, int RPL, bool BOUNDED, class Rule = RuleLife>
+__device__ __forceinline__ void wave_generation(uint32_t (&w)[RPL][NW], const WaveGeom& g, Rule rule = Rule()) {
     uint32_t s[RPL][NW], c[RPL][NW];
 #pragma unroll
     for (int i = 0; i < RPL; i++) ragged_row_sum<NW, BOUNDED>(w[i], g.lb, g.lbbit, s[i], c[i]);
@@ -81,16 +96,27 @@ __device__ __forceinline__ void wave_generation(uint32_t (&w)[RPL][NW], const Wa
         ds[j] = bperm(g.dn_addr, s[0][j]) & g.dn_mask;
         dc[j] = bperm(g.dn_addr, c[0][j]) & g.dn_mask;
     }
+    if constexpr (std::is_same<Rule, RuleLife>::value) {
 #pragma unroll
-    for (int i = 0; i < RPL; i++)
+        for (int i = 0; i < RPL; i++)
 #pragma unroll
-        for (int j = 0; j < NW; j++) {
-            const uint32_t sP = i == 0 ? us[j] : s[i - 1][j], cP = i == 0 ? uc[j] : c[i - 1][j];
-            const uint32_t sN = i == RPL - 1 ? ds[j] : s[i + 1][j], cN = i == RPL - 1 ? dc[j] : c[i + 1][j];
-            uint32_t v = life_next(sP, cP, s[i][j], c[i][j], sN, cN, w[i][j]);
-            if (j == NW - 1) v &= g.lastmask;
-            w[i][j] = v;
+            for (int j = 0; j < NW; j++) {
+                const uint32_t sP = i == 0 ? us[j] : s[i - 1][j], cP = i == 0 ? uc[j] : c[i - 1][j];
+                const uint32_t sN = i == RPL - 1 ? ds[j] : s[i + 1][j], cN = i == RPL - 1 ? dc[j] : c[i + 1][j];
+                uint32_t v = life_next(sP, cP, s[i][j], c[i][j], sN, cN, w[i][j]);
+                if (j == NW - 1) v &= g.lastmask;
+                w[i][j] = v;
+            }
+    } else {
+#pragma unroll
+        for (int i = 0; i < RPL; i++) {
+            uint32_t v[NW];
+            rule_next_row<NW>(i == 0 ? us : s[i - 1], i == 0 ? uc : c[i - 1], s[i], c[i], i == RPL - 1 ? ds : s[i + 1],
+                              i == RPL - 1 ? dc : c[i + 1], w[i], rule.packed, v);
+#pragma unroll
+            for (int j = 0; j < NW; j++) w[i][j] = j == NW - 1 ? v[j] & g.lastmask : v[j];
         }
+    }
 }
 
 // Sum of v over the wave's 64 lanes, the same value in every lane: four DPP adds leave every lane of a row of 16 with

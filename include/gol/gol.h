@@ -274,8 +274,9 @@ int gol_batch_seed_dotnet(gol_batch* b, const int32_t* seeds, int64_t n, int mod
 /* Board i gets the cells gol_seed_splitmix(seed + i) gives a single board of this size. */
 int gol_batch_seed_splitmix(gol_batch* b, uint64_t seed);
 int gol_batch_clear(gol_batch* b);
-/* Every board advances `generations` (>= 0; 0 is a no-op) synchronous B3/S23 generations in one launch: a wavefront
- * loads its board, runs every generation in registers and stores it.  Asynchronous; any readback synchronises. */
+/* Every board advances `generations` (>= 0; 0 is a no-op) synchronous generations under the batch's rule (B3/S23
+ * unless gol_ensemble_set_rule said otherwise) in one launch: a wavefront loads its board, runs every generation in
+ * registers and stores it.  Asynchronous; any readback synchronises. */
 int gol_batch_step(gol_batch* b, int64_t generations);
 /* As gol_batch_step between two HIP timing events on the batch's stream, synchronised: the call's device time. */
 int gol_batch_step_timed(gol_batch* b, int64_t generations, double* elapsed_us);
@@ -291,9 +292,32 @@ int gol_batch_hashes(gol_batch* b, uint64_t* out, int64_t n);
 /* One board's frame, as gol_render_gray8: pixels[x + y*stride] = alive ? alive_value : 0, stride >= width. */
 int gol_batch_render_gray8(gol_batch* b, int64_t board, uint8_t* pixels, int64_t stride, uint8_t alive_value);
 int gol_batch_synchronize(gol_batch* b);
+/* Life-like rules (B.../S...).  A rule is two 9-bit masks: bit n (0..8) of `birth` set = a dead cell with n live cells
+ * among its 8 neighbours becomes alive; bit n of `survive` set = a live cell with n live neighbours stays alive.
+ *   gol_rule_parse   host-only, pure.  Accepts, in any letter case and with blanks around it, "B<digits>/S<digits>",
+ *     the halves swapped ("S23/B3") and the digits-only survival/birth form ("23/3"); either list may be empty
+ *     ("B2/S", "B/S"); digits 0..8, each at most once per list, in any order.  Everything else -- NULL, the empty
+ *     string, a 9, a repeated digit, a missing slash, a third field ("B3/S23/3"), any other character, more than 31
+ *     characters -- is GOL_ERR_INVALID with both outputs untouched.
+ *   gol_rule_format  host-only, pure.  The canonical "B<ascending digits>/S<ascending digits>" and its NUL; len >= 22.
+ *     A mask outside 0..0x1FF or a short buffer is GOL_ERR_INVALID.  parse(format(b, s)) == (b, s) for every rule.
+ *   gol_ensemble_set_rule / gol_ensemble_rule  named as gol_ensemble_cycles is: the rule is the ensemble's, and they
+ *     take the batch as their argument.  Masks in 0..0x1FF, anything else GOL_ERR_INVALID with the batch's rule as it
+ *     was.  A new batch is B3/S23.  The rule is a property of the handle and changes only the future: cells, the generation counter,
+ *     populations and hashes are untouched, and set_cells, the seeds and clear keep it.  It is the rule of
+ *     gol_batch_step, gol_batch_step_timed, gol_batch_step_trace and gol_ensemble_cycles.
+ *   Boundaries: on a bounded board the cells outside are dead forever and are no cells of the board, also under a rule
+ *     with B0; on a torus every cell has 8 neighbours (on a 3-wide or 3-high torus the other cells of the 3-line).
+ * The gol_board handle is B3/S23 only. */
+#define GOL_RULE_LIFE_BIRTH 0x008
+#define GOL_RULE_LIFE_SURVIVE 0x00C
+int gol_rule_parse(const char* text, int* birth, int* survive);
+int gol_rule_format(int birth, int survive, char* out, int64_t len);
+int gol_ensemble_set_rule(gol_batch* b, int birth, int survive);
+int gol_ensemble_rule(gol_batch* b, int* birth, int* survive);
 /* The ensemble's cycle census: for every board, after how many generations it enters a cycle and of
  * what period, one launch, one wavefront per board, the search in that wave's registers.
- *   Definition: B_0 = board i's current cells, B_(t+1) = the next B3/S23 generation of B_t under the batch's boundary;
+ *   Definition: B_0 = board i's current cells, B_(t+1) = the next generation of B_t under the batch's rule and boundary;
  *     t* = the smallest t >= 1 with B_t = B_s for some s < t; transient mu = s, period lambda = t* - mu (minimal).
  *     Resolved, exactly when t* = mu + lambda <= max_generations: transient[i] = mu, period[i] = lambda, population[i] =
  *     live cells of B_mu.  Unresolved, exactly when t* > max_generations: transient[i] = -1, period[i] = 0,

@@ -110,6 +110,23 @@ class Batch {
         check(gol_batch_get_cells(b_, first, n, c.data(), (int64_t)c.size()), "gol_batch_get_cells");
         return c;
     }
+    // the rule of every later step, stepTrace and cycles (B3/S23 until set): "B36/S23", "S23/B36" or "23/36"
+    Batch& setRule(const std::string& rule) {
+        int birth = 0, survive = 0;
+        check(gol_rule_parse(rule.c_str(), &birth, &survive), "gol_rule_parse");
+        return setRule(birth, survive);
+    }
+    Batch& setRule(int birth, int survive) {  // 9-bit masks, bit n = n live neighbours
+        check(gol_ensemble_set_rule(b_, birth, survive), "gol_ensemble_set_rule");
+        return *this;
+    }
+    std::string rule() const {  // canonical: "B36/S23"
+        int birth = 0, survive = 0;
+        char text[22];
+        check(gol_ensemble_rule(b_, &birth, &survive), "gol_ensemble_rule");
+        check(gol_rule_format(birth, survive, text, sizeof text), "gol_rule_format");
+        return text;
+    }
     Batch& step(int64_t generations = 1) {
         check(gol_batch_step(b_, generations), "gol_batch_step");
         return *this;
