@@ -15,6 +15,9 @@
 //             next = (t == 3) | (alive & t == 4).  A = xor3(s), B = maj3(s), X = xor3(c), Y = maj3(c)
 //             then a 3-LUT tree found by exhaustive search (tests/cpp/test_bitlogic.cpp re-checks all 2^9
 //             neighbourhoods):  o1 = L(A, Y, alive; 0x27), o2 = L(B, X, Y; 0x19), next = L(o1, o2, A; 0x24).
+//   row pairs the pipelined pass (gol_pipe.hip) takes its rows two at a time and shares the vertical sum of the two rows
+//             both outputs hold (pair_sum / life_next_pair below): 2 + 2 + 4 = 8 LUT ops per word and generation
+//             instead of 2 + 4 + 3 = 9, i.e. 12 VALU ops with the caller's shifts and moves at one word per block.
 //
 // LUT convention used in this file: lut3(a, b, c, L) = bit (a | b<<1 | c<<2) of L.  gfx950's
 // v_bitop3_b32 indexes its immediate with (S0<<2 | S1<<1 | S2), so a -> S2 and c -> S0.
@@ -84,6 +87,37 @@ GOL_HD uint32_t life_next(uint32_t sP, uint32_t cP, uint32_t sC, uint32_t cC, ui
     const uint32_t o1 = lut3<0x27>(A, Y, alive);
     const uint32_t o2 = lut3<0x19>(B, X, Y);
     return lut3<0x24>(o1, o2, A);
+}
+
+// ---- two output rows at once: 8 LUT ops per word and generation (the pipelined pass, gol_pipe.hip).
+//
+// Rows n and n + 1 entering a level give the outputs of rows n - 1 and n, and both 9-cell totals hold the same two
+// middle rows:  t(n - 1) = row(n - 2) + [row(n - 1) + row(n)],  t(n) = [row(n - 1) + row(n)] + row(n + 1).
+// pair_sum adds the shared pair once, as a 3-bit number q = q0 + 2 q1 + 4 q2 = (s1 + 2 c1) + (s2 + 2 c2) in 0..6
+// (4 ops per word for two output rows); life_next_pair finishes one output from q, the remaining row's sum (s, c) and
+// the output's own centre word (4 ops), so 2 (row sum) + 2 + 4 = 8 against life_next's 2 + 7.
+//   t = q + s + 2 c  (0..9);  next = (t == 3) | (alive & t == 4), as life_next.
+//   g1 = L(q0, s, alive; 0xE6) = alive ? q0 | s : q0 ^ s     -- t's low bit for a dead cell, "t0 or a carry" for a live
+//   g2 = L(q2, alive, g1; 0x5C),  g3 = L(q1, q2, c; 0x25),  next = L(g1, g2, g3; 0x48)
+// a 4-LUT circuit found by exhaustive search over the reachable inputs.  It relies on two don't-cares that hold by
+// construction: q != 7 (two 2-bit row sums of at most 3 each), and alive => q >= 1 (the centre word is one of the pair's
+// two rows, and a live centre is counted in its own row's sum).  Outside them the circuit is NOT life_next: `alive` must
+// be the centre word of a row whose sum went into q.  tests/cpp/test_bitlogic_pair.cpp checks both outputs against
+// life_next over all 2^12 fillings of a 4 x 3 neighbourhood and over random words on a small interleaved torus.
+GOL_HD void pair_sum(uint32_t s1, uint32_t c1, uint32_t s2, uint32_t c2, uint32_t& q0, uint32_t& q1, uint32_t& q2) {
+    // Two-input ops written as LUTs that ignore their third input (0x88 = a & b, 0x66 = a ^ b): the compiler emits
+    // `s1 & s2` and `s1 ^ s2` as 4-byte v_and_b32 / v_xor_b32, and a 4-byte instruction inside one of the pipelined
+    // pass's levels flips the address parity of every 8-byte instruction after it (gol_pipe.hip level_align)
+    const uint32_t k = lut3<0x88>(s1, s2, s2);
+    q0 = lut3<0x66>(s1, s2, s2);
+    q1 = lut3<0x96>(c1, c2, k);
+    q2 = lut3<0xE8>(c1, c2, k);
+}
+GOL_HD uint32_t life_next_pair(uint32_t q0, uint32_t q1, uint32_t q2, uint32_t s, uint32_t c, uint32_t alive) {
+    const uint32_t g1 = lut3<0xE6>(q0, s, alive);
+    const uint32_t g2 = lut3<0x5C>(q2, alive, g1);
+    const uint32_t g3 = lut3<0x25>(q1, q2, c);
+    return lut3<0x48>(g1, g2, g3);
 }
 
 // ---- any life-like rule (gol_rule.h: birth | survive << 9, uniform over a launch) on N words of one row at a time.

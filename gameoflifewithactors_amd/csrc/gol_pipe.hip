@@ -11,8 +11,10 @@
 //   stage s     pushes each row through its D levels (the same level-fenced schedule as the streaming pass) and hands its
 //               level-(s + 1) D rows to stage s + 1 through a ring of LDS rows,
 //   stage S - 1 stores level K.
-// A wave's window is 5 D M = 80 VGPRs at (D, M) = (4, 4): 122-124 VGPRs in all, 4 waves per SIMD.  A pipeline streams its
+// A wave's window is 5 D M = 80 VGPRs at (D, M) = (4, 4): 119-122 VGPRs in all, 4 waves per SIMD.  A pipeline streams its
 // segment once, so the recomputed halo rows are one cone per pipeline (K (K - 1) level-rows), not one per wave.
+// A level takes its rows in pairs and adds the two rows both outputs of a pair hold once (gol_bitlogic.h pair_sum /
+// life_next_pair): 8 + 8 / M = 10 issue slots per word and generation here.
 //
 // Ring protocol (per pipeline and stage boundary, no workgroup barrier): the producer writes output row j into slot
 // j mod NR and then publishes prod = rows written; the consumer waits for prod, reads the rows, and publishes
@@ -139,14 +141,17 @@ __device__ __forceinline__ void lds_read_trip(uint32_t base, u32x4& r0, u32x4& r
         : "v"(base), "i"(kRowBytes), "i"(2 * kRowBytes), "i"(3 * kRowBytes)
         : "memory");
 }
-// A level is 160 8-byte instructions back to back (v_bitop3, v_alignbit, DPP moves), and the pass's speed follows the
-// address they start at, modulo 8: this is the 25 % that once seemed to follow the poll loops' address (lds_wait).
+// A level is 144 8-byte instructions back to back (v_bitop3, v_alignbit, DPP moves; 160 before the row-pair rule), and
+// the pass's speed follows the address they start at, modulo 8: this is the 25 % that once seemed to follow the poll
+// loops' address (lds_wait).
 // Measured, not explained (profiles/pipe_trips/; addresses by llvm-objdump -d of the device object):
 //   levels starting at 4 (mod 8)  993-1004 us per 65536^2 torus pass  (GOL_PIPE_LEVEL_PAD 1, the default)
 //   levels starting at 0 (mod 8)  1235-1249 us                        (GOL_PIPE_LEVEL_PAD 0)
-// and the same on the parent's kernel with nothing but this pin added (1019-1023 against 1221-1255).  So every level
+// and the same on the parent's kernel with nothing but this pin added (1019-1023 against 1221-1255), and again with the
+// row-pair rule (932-942 against 1158-1167, profiles/pair_rule/).  So every level
 // starts GOL_PIPE_LEVEL_PAD 4-byte nops past an 8-byte boundary, whatever code comes before it.  The pad is right for
-// the code this compiler emits (no 4-byte instruction at a level's head or inside it); DESIGN records the tally of
+// the code this compiler emits (no 4-byte instruction at a level's head or inside it: pair_sum's two-input ops are
+// written as LUTs for that reason); DESIGN records the tally of
 // addresses a rebuild should reproduce -- if a compiler moves it, measure before touching the pad: the fast case is
 // the one OFF the boundaries.
 #ifndef GOL_PIPE_LEVEL_PAD
@@ -414,18 +419,21 @@ void gol_pipe_step(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst,
         for (int g = 0; g < D; g++) {
 #pragma unroll
             for (int r = 0; r < kR; r += 2) {
-                uint32_t o0[kM], o1[kM], sN[kM], cN[kM];
+                // rows Y and r are the middle rows of both outputs: their sum once (pair_sum), then row Y's output with
+                // X and row r's with r + 1 (gol_bitlogic.h: 8 LUT ops per word and generation)
+                uint32_t o0[kM], o1[kM], sN[kM], cN[kM], q0[kM], q1[kM], q2[kM];
                 row_sum_block<kM>(v[r], from_left<BND>(v[r][kM - 1]), right[r], sN, cN);
 #pragma unroll
                 for (int j = 0; j < kM; j++) {
-                    o0[j] = life_next(sX[g][j], cX[g][j], sY[g][j], cY[g][j], sN[j], cN[j], aY[g][j]);
+                    pair_sum(sY[g][j], cY[g][j], sN[j], cN[j], q0[j], q1[j], q2[j]);
+                    o0[j] = life_next_pair(q0[j], q1[j], q2[j], sX[g][j], cX[g][j], aY[g][j]);
                     sX[g][j] = sN[j];
                     cX[g][j] = cN[j];
                 }
                 row_sum_block<kM>(v[r + 1], from_left<BND>(v[r + 1][kM - 1]), right[r + 1], sN, cN);
 #pragma unroll
                 for (int j = 0; j < kM; j++) {
-                    o1[j] = life_next(sY[g][j], cY[g][j], sX[g][j], cX[g][j], sN[j], cN[j], v[r][j]);
+                    o1[j] = life_next_pair(q0[j], q1[j], q2[j], sN[j], cN[j], v[r][j]);
                     sY[g][j] = sN[j];
                     cY[g][j] = cN[j];
                 }
