@@ -109,6 +109,11 @@ extern int gol_rule_format(int birth, int survive, byte[] out, int64 len)   // l
 extern int gol_ensemble_set_rule(nativeint batch, int birth, int survive)
 [<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
 extern int gol_ensemble_rule(nativeint batch, int& birth, int& survive)
+// ... and of a single board (B3/S23 until set; boards on several GPUs take B3/S23 only)
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int gol_set_rule(nativeint board, int birth, int survive)
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int gol_rule(nativeint board, int& birth, int& survive)
 [<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
 extern nativeint gol_last_error()
 
@@ -123,6 +128,12 @@ type Board(width: int, height: int, boundary: Boundary, ?numGpus: int) =
     do check "gol_create" (gol_create(int64 width, int64 height, int boundary, defaultArg numGpus 1, 0, &h))
     member _.Seed(seed: int, mode: InitMode) = check "gol_seed_dotnet" (gol_seed_dotnet(h, seed, int mode))
     member _.Step(generations: int64) = check "gol_step" (gol_step(h, generations))
+    /// "B36/S23", "S23/B36" or "23/36": the rule of every later Step (B3/S23 until set)
+    member _.SetRule(rule: string) =
+        let mutable birth = 0
+        let mutable survive = 0
+        check "gol_rule_parse" (gol_rule_parse(rule, &birth, &survive))
+        check "gol_set_rule" (gol_set_rule(h, birth, survive))
     member _.GetCells() =
         let a = Array.zeroCreate<byte> (width * height)
         check "gol_get_cells" (gol_get_cells(h, a, int64 a.Length)); a

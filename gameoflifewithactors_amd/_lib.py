@@ -179,6 +179,9 @@ SIGNATURES = {
     "gol_rule_format": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_char_p, i64]),
     "gol_ensemble_set_rule": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int]),
     "gol_ensemble_rule": (ctypes.c_int, [vp, ip, ip]),
+    # ... and of a single board
+    "gol_set_rule": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int]),
+    "gol_rule": (ctypes.c_int, [vp, ip, ip]),
     # test and A/B knobs (csrc/gol_debug.h: internal, not part of the gol.h boundary)
     "gol_debug_batch_group_waves": (ctypes.c_int, [vp, ctypes.c_int]),
     "gol_debug_ensemble_cycles_us": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_double)]),
@@ -193,7 +196,7 @@ SIGNATURES = {
 # Names gol_debug_set_option / gol_debug_get_option take (csrc/gol_debug.h); Board.set_option routes them there.
 # The library exports its own list (gol_debug_option_names); tests/test_cpu_host.py checks this one against it.
 DEBUG_OPTIONS = frozenset({"coop_epoch", "coop_spin_limit", "coop_r", "resident_threads", "coop_launch",
-                           "lanes_launches", "last_pass"})
+                           "lanes_launches", "last_pass", "rule_table", "rule_seg_rows", "rule_k"})
 
 
 def _elf_sections(data: bytes, base: int = 0):

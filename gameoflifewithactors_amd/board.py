@@ -42,10 +42,11 @@ class Board:
     devices: explicit strip placement (``gol_create_multi``), e.g. ``[0, 0, 0]`` runs three strips on one GPU.
     ilv: packed layout, words per interleaved block (0 = library default for the width; 1, 2, 4).
     options: {name: value} passed to gol_set_option after creation (e.g. {"coop": 0}).
+    rule: a life-like rule as ``set_rule`` takes it ("B36/S23", ...); B3/S23 unless named.
     """
 
     def __init__(self, width: int, height: int, boundary: int = TORUS, tblock_k: int = 0, num_gpus: int = 1,
-                 ilv: int = 0, devices=None, options: dict | None = None):
+                 ilv: int = 0, devices=None, options: dict | None = None, rule="B3/S23"):
         self._lib = _lib.load()
         h = ctypes.c_void_p()
         if devices is not None:
@@ -61,6 +62,8 @@ class Board:
         try:
             for name, value in (options or {}).items():
                 self.set_option(name, value)
+            if rule != "B3/S23":
+                self.set_rule(rule)
         except Exception:
             self.close()
             raise
@@ -148,14 +151,17 @@ class Board:
         return self
 
     def save(self, path: str) -> None:
-        """Write a snapshot file (patterns.write_snapshot): header + canonical rows, 1 bit per cell."""
+        """Write a snapshot file (patterns.write_snapshot): header + canonical rows, 1 bit per cell.  The board's rule
+        is a property of the handle, not of the cells, and the file does not carry it: pass ``rule=`` to
+        ``from_snapshot`` (or call ``set_rule``) when restoring."""
         patterns.write_snapshot(path, self.save_packed(), self.width, self.height, self.boundary, self.generation,
                                 self.hash())
 
     @classmethod
     def from_snapshot(cls, path: str, **kw) -> "Board":
         """A new board holding a snapshot file's cells (same size and boundary); the canonical hash recorded
-        in the file is checked after the upload.  kw: tblock_k, num_gpus, ilv, devices."""
+        in the file is checked after the upload.  kw: tblock_k, num_gpus, ilv, devices, options, rule (a snapshot holds
+        cells only: the new board is B3/S23 unless ``rule`` says otherwise)."""
         head, words = patterns.read_snapshot(path)
         b = cls(head["width"], head["height"], head["boundary"], **kw)
         b.load_packed(words)
@@ -193,6 +199,24 @@ class Board:
         v = ctypes.c_int64()
         check(getattr(self._lib, fn)(self._h, name.encode(), ctypes.byref(v)), f"{fn}({name})")
         return v.value
+
+    # ---------------------------------------------------------------- rule
+    def set_rule(self, rule) -> "Board":
+        """The rule of every later ``step`` and ``step_timed``: a string ("B36/S23", "S23/B36", "23/36"; ValueError for
+        anything else) or a ``(birth, survive)`` pair of 9-bit masks (bit n = n live neighbours).  Cells, the
+        generation counter, population and hash stay as they are, and set_cells, the seeds, load_packed, place_rle and
+        clear keep the rule.  On a bounded board the cells outside stay dead under any rule, B0 included.  A board on
+        several GPUs takes B3/S23 only (NotImplementedError)."""
+        birth, survive = _lib.rule_parse(rule) if isinstance(rule, (str, bytes)) else rule
+        check(self._lib.gol_set_rule(self._h, int(birth), int(survive)), "gol_set_rule")
+        return self
+
+    @property
+    def rule(self) -> str:
+        """The board's rule in canonical form, "B3/S23" for a new board."""
+        b, s = ctypes.c_int(), ctypes.c_int()
+        check(self._lib.gol_rule(self._h, ctypes.byref(b), ctypes.byref(s)), "gol_rule")
+        return _lib.rule_format(b.value, s.value)
 
     # ---------------------------------------------------------------- stepping
     def step(self, generations: int = 1) -> "Board":

@@ -12,6 +12,7 @@
 #include "../../include/gol/gol.h"
 #include "gol_internal.h"
 #include "gol_multi.h"
+#include "gol_rule.h"
 
 namespace gol {
 
@@ -90,7 +91,7 @@ struct EventPair {
 };
 
 // The pass a gol_step call takes (choose_pass); its value is the debug option "last_pass" (gol_debug.h).
-enum class Pass { None, Wave, Lanes, Coop, CoopRagged, Ring, StreamRagged, Resident, Bytes, Stream, Multi };
+enum class Pass { None, Wave, Lanes, Coop, CoopRagged, Ring, StreamRagged, Resident, Bytes, Stream, Multi, RuleStream };
 
 extern const int64_t kCoopMaxCells;               // gol_policy.cpp
 constexpr int kCoopFlagWords = 1024;              // bands of one launch at most (one per CU) ...
@@ -133,6 +134,11 @@ struct BoardOptions {
                                               // gol_internal.h launch_persistent)
     bool view_stream = true;                  // "view_stream": wide-tile views on the streaming kernel (gol_view.hip);
                                               // 0 = every view on the per-pixel kernel
+    bool rule_table = false;                  // "rule_table" (gol_debug.h): a B3/S23 board runs the rule family's passes
+                                              // too (any other rule always does)
+    int64_t rule_seg_rows = 0;                // "rule_seg_rows" (gol_debug.h): rows per wave segment of the rule-generic
+                                              // streaming pass (0 = planned)
+    int rule_k = 0;                           // "rule_k" (gol_debug.h): its deepest pass, 8, 4, 2 or 1 (0 = by layout)
 };
 
 }  // namespace gol
@@ -172,11 +178,15 @@ struct gol_board {
     int rag_ilv = 1;
     int ring_age = 0;  // ring rows: generations since the copies were last exact (errors reach ring_age cells in)
     int64_t generation = 0;
+    uint32_t rule = gol::kRuleLifePacked;  // birth | survive << 9 (gol_rule.h rule_pack): B3/S23 until gol_set_rule
     gol::MultiBoard* multi = nullptr;  // num_gpus > 1: row strips over several devices (gol_multi.h)
 
     size_t bytes() const { return packed ? (size_t)(pitch * H) * 4 : (size_t)(W * H); }
     uint32_t* words(int i) { return static_cast<uint32_t*>(buf[i]); }
     uint8_t* cells(int i) { return static_cast<uint8_t*>(buf[i]); }
+
+    // the rule family's passes (choose_pass): any rule but B3/S23, or B3/S23 with the "rule_table" knob
+    bool rule_family() const { return opt.rule_table || rule != gol::kRuleLifePacked; }
 
     gol::StreamArgs stream_args(int64_t out_begin, int64_t out_end, int k) const {
         gol::StreamArgs a{};

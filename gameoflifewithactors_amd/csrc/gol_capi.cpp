@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "gol_board.h"
+#include "gol_rule.h"
 #include "gol_seed_rle.h"
 #include "gol_view.h"
 
@@ -634,6 +635,31 @@ int gol_hash(gol_board* b, uint64_t* out) {
         if (!out) return fail(GOL_ERR_INVALID, "null out");
         return reduce_impl(b, true, out);
     });
+}
+
+// The board's rule (gol.h).  A property of the handle: nothing that writes cells touches it.
+int gol_set_rule(gol_board* b, int birth, int survive) {
+    return with_board(b, [&] {
+        if (!gol::rule_masks_ok(birth, survive))
+            return fail(GOL_ERR_INVALID, "rule: birth and survive masks must lie in 0..0x1FF");
+        const uint32_t rule = gol::rule_pack(birth, survive);
+        if (b->multi && rule != gol::kRuleLifePacked)
+            return fail(GOL_ERR_UNSUPPORTED, "rule: a board on several GPUs runs B3/S23 only (its strip passes are the "
+                                             "B3/S23 streaming kernels); the rule is unchanged");
+        // no ragged multi-generation pass runs under another rule: the bytes are the state from here on
+        if (!b->multi) GOL_RC(sync_bytes(b));
+        b->rule = rule;
+        return GOL_OK;
+    });
+}
+
+int gol_rule(gol_board* b, int* birth, int* survive) {
+    if (!b) return fail(GOL_ERR_INVALID, "null board");
+    if (!birth || !survive) return fail(GOL_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> g(b->mu);
+    *birth = (int)(b->rule & gol::kRuleMaskMax);
+    *survive = (int)(b->rule >> 9);
+    return GOL_OK;
 }
 
 int gol_device_count(int* n) {

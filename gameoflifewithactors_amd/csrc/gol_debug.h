@@ -15,7 +15,15 @@
  *   "last_pass"                 (read-only) the pass the last gol_step / gol_step_timed call took, as gol::Pass
  *                               (gol_board.h): 0 none yet, 1 single-wave, 2 rows-on-lanes, 3 cooperative, 4 cooperative on
  *                               a ragged board's scratch rows, 5 block (ring) rows, 6 ragged streaming, 7 LDS-resident,
- *                               8 byte step, 9 streaming, 10 multi-part
+ *                               8 byte step, 9 streaming, 10 multi-part, 11 rule-generic streaming
+ *   "rule_table" 0 | 1          1: a B3/S23 board runs the passes of the rule family too (single-wave with the rule
+ *                               table, rule-generic streaming, byte step under the rule), as any other rule always
+ *                               does.  Results are identical: the knob is what lets the rule arithmetic be checked
+ *                               against the B3/S23 passes and the committed goldens, and timed against them
+ *                               (DESIGN.md 4.12).  Multi-part boards refuse 1 (GOL_ERR_UNSUPPORTED)
+ *   "rule_k" 0 | 1 | 2 | 4 | 8  the deepest pass of the rule-generic streaming pass (0: by layout; A/B)
+ *   "rule_seg_rows" 0 | n       rows per wave segment of the rule-generic streaming pass (0: planned): small test
+ *                               boards get several segments
  * Unknown names return GOL_ERR_INVALID.
  */
 #ifndef GOL_DEBUG_H

@@ -40,6 +40,32 @@ __global__ __launch_bounds__(256) void gol_bytes_step(const uint8_t* __restrict_
     dst[idx] = (n == 3) | ((n == 2) & alive);
 }
 
+// The same step under any life-like rule (gol_rule.h): next = (alive ? survive : birth) >> n & 1.  Cells outside a
+// bounded board are never read and never written, so no rule can make one live.
+template <bool BOUNDED>
+__global__ __launch_bounds__(256) void gol_bytes_rule_step(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                                            int64_t W, int64_t H, uint32_t birth, uint32_t survive) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= W * H) return;
+    const int64_t x = idx % W, y = idx / W;
+    int n = 0;
+#pragma unroll
+    for (int dy = -1; dy <= 1; dy++)
+#pragma unroll
+        for (int dx = -1; dx <= 1; dx++) {
+            if (!dx && !dy) continue;
+            int64_t nx = x + dx, ny = y + dy;
+            if (BOUNDED) {
+                if (nx < 0 || nx >= W || ny < 0 || ny >= H) continue;
+            } else {
+                nx = nx < 0 ? nx + W : (nx >= W ? nx - W : nx);
+                ny = ny < 0 ? ny + H : (ny >= H ? ny - H : ny);
+            }
+            n += src[nx + ny * W] != 0;
+        }
+    dst[idx] = (uint8_t)(((src[idx] != 0 ? survive : birth) >> n) & 1u);
+}
+
 // ------------------------------------------------------------------------------------------------
 // Packed formats.  `pitch` = words per buffer row; owned row y lives at buffer row `row0 + y`.
 
@@ -476,6 +502,18 @@ hipError_t launch_bytes_step(const uint8_t* src, uint8_t* dst, int64_t W, int64_
         hipLaunchKernelGGL((gol_bytes_step<true>), dim3(grid1d(W * H)), dim3(256), 0, s, src, dst, W, H);
     else
         hipLaunchKernelGGL((gol_bytes_step<false>), dim3(grid1d(W * H)), dim3(256), 0, s, src, dst, W, H);
+    return hipGetLastError();
+}
+
+hipError_t launch_bytes_rule_step(const uint8_t* src, uint8_t* dst, int64_t W, int64_t H, bool bounded, int birth,
+                                  int survive, hipStream_t s) {
+    if (birth < 0 || birth > 0x1FF || survive < 0 || survive > 0x1FF) return hipErrorInvalidValue;
+    if (bounded)
+        hipLaunchKernelGGL((gol_bytes_rule_step<true>), dim3(grid1d(W * H)), dim3(256), 0, s, src, dst, W, H,
+                           (uint32_t)birth, (uint32_t)survive);
+    else
+        hipLaunchKernelGGL((gol_bytes_rule_step<false>), dim3(grid1d(W * H)), dim3(256), 0, s, src, dst, W, H,
+                           (uint32_t)birth, (uint32_t)survive);
     return hipGetLastError();
 }
 

@@ -108,8 +108,18 @@ int* pipe_error_word();  // the library's own error word (strip passes), device 
 // reads inside the buffer without a wrap or clamp, lane offsets in 32 bits.  Returns the violations found.
 int64_t pipe_check_plan(const PipeArgs& a, int k, bool wrap);
 
+// ---- gol_rule_step.hip: the rule-generic streaming pass (any life-like rule, packed boards of any size and layout;
+// plan in gol_rule_plan.h).  k is 8, 4, 2 or 1 (rule_stream_largest_k(n): the deepest that n generations hold); rule: the packed masks (gol_rule.h rule_pack); seg_opt: rows per wave segment, 0 = planned.
+int rule_stream_largest_k(int64_t n);
+int rule_stream_max_k(int ilv);  // the deepest pass a layout runs by default
+hipError_t launch_rule_stream(const uint32_t* src, uint32_t* dst, int64_t W, int64_t H, int64_t pitch, int ilv, int k,
+                              bool bounded, uint32_t rule, int64_t seg_opt, hipStream_t s);
+
 // ---- gol_formats.hip
 hipError_t launch_bytes_step(const uint8_t* src, uint8_t* dst, int64_t W, int64_t H, bool bounded, hipStream_t s);
+// the same step under any life-like rule (birth, survive: the 9-bit masks of gol_rule.h)
+hipError_t launch_bytes_rule_step(const uint8_t* src, uint8_t* dst, int64_t W, int64_t H, bool bounded, int birth,
+                                  int survive, hipStream_t s);
 hipError_t launch_pack(const uint8_t* cells, uint32_t* words, int64_t W, int64_t rows, int64_t pitch, int64_t row0,
                        int ilv, hipStream_t s);
 // byte board (any width W) <-> consecutive words, `pitch` words per row: bit b of word j = cell 32 j + b, cells past
@@ -239,8 +249,12 @@ hipError_t launch_lanes_pass(const uint32_t* src, uint32_t* dst, int64_t W, int6
 
 // ---- gol_wave.hip: whole board in one wavefront's registers (W <= 128, H <= 256), all generations in one launch
 int wave_resident_rpl(int64_t W, int64_t H);  // rows per lane, 0 = the board does not fit
+// ... under the rule family (any rule but B3/S23, or "rule_table"): every board up to 128 x 256, the last lane partly
+// filled where the rows do not divide into lanes
+int wave_rule_rpl(int64_t W, int64_t H);
+// rule: the packed masks (gol_rule.h rule_pack); force_table: B3/S23 through the rule-table family too
 hipError_t launch_wave_resident(const void* src, void* dst, int64_t W, int64_t H, int64_t pitch, int64_t gens,
-                                bool bounded, bool bytes, hipStream_t s);
+                                bool bounded, bool bytes, uint32_t rule, bool force_table, hipStream_t s);
 
 // ---- gol_batch.hip: `count` boards of one single-wave geometry (wave_resident_rpl) back to back, NW = ceil(W / 32)
 // words per row, bits past W zero; one wavefront per board; count <= kBatchCountMax (gol_batch_host.h)

@@ -102,6 +102,21 @@ const Option kOptions[] = {
     {"coop_launch", kDebug, get<&O::coop_launch>, set_flag<&O::coop_launch>},
     {"lanes_launches", kDebug, [](const gol_board* b) -> int64_t { return b->lanes_launches; }, nullptr},
     {"last_pass", kDebug, [](const gol_board* b) -> int64_t { return (int64_t)b->last_pass; }, nullptr},
+    {"rule_table", kDebug, get<&O::rule_table>,
+     [](gol_board* b, int64_t v) {
+         if (v != 0 && v != 1) return fail(GOL_ERR_INVALID, "rule_table must be 0 or 1");
+         if (v && b->multi) return fail(GOL_ERR_UNSUPPORTED, "rule_table: a multi-part board runs B3/S23 on its strip passes only");
+         // no ragged multi-generation pass runs in the rule family: the bytes first (as gol_set_rule)
+         if (!b->multi) GOL_RC(sync_bytes(b));
+         return set_flag<&O::rule_table>(b, v);
+     }},
+    {"rule_k", kDebug, get<&O::rule_k>,
+     [](gol_board* b, int64_t v) {
+         if (v != 0 && v != 1 && v != 2 && v != 4 && v != 8) return fail(GOL_ERR_INVALID, "rule_k must be 0, 1, 2, 4 or 8");
+         return set_any<&O::rule_k>(b, v);
+     }},
+    {"rule_seg_rows", kDebug, get<&O::rule_seg_rows>,
+     [](gol_board* b, int64_t v) { return set_any<&O::rule_seg_rows>(b, v < 0 ? 0 : v); }},
 };
 
 // One option call: reads into *value (`get`) or stores it.  `debug`: through the gol_debug_* entry points, which know

@@ -128,7 +128,7 @@ int ensure_rag(gol_board* b, int64_t need) {
 int run_wave(gol_board* b, int64_t gens) {
     return ping_pong(b, &b->cur, gens, at_most(kResidentMaxGensPerLaunch), [&](int64_t g) {
         GOL_HIP(gol::launch_wave_resident(b->buf[b->cur], b->buf[b->cur ^ 1], b->W, b->H, b->pitch, g,
-                                          b->boundary == GOL_BOUNDED, !b->packed, b->stream));
+                                          b->boundary == GOL_BOUNDED, !b->packed, b->rule, b->opt.rule_table, b->stream));
         return GOL_OK;
     });
 }
@@ -233,11 +233,31 @@ int run_resident(gol_board* b, int64_t gens) {
 }
 
 int run_bytes(gol_board* b, int64_t gens) {
+    const bool rule = b->rule_family();
     return ping_pong(b, &b->cur, gens, at_most(1), [&](int64_t) {
-        GOL_HIP(gol::launch_bytes_step(b->cells(b->cur), b->cells(b->cur ^ 1), b->W, b->H, b->boundary == GOL_BOUNDED,
-                                       b->stream));
+        if (rule)
+            GOL_HIP(gol::launch_bytes_rule_step(b->cells(b->cur), b->cells(b->cur ^ 1), b->W, b->H,
+                                                b->boundary == GOL_BOUNDED, (int)(b->rule & 0x1FF), (int)(b->rule >> 9),
+                                                b->stream));
+        else
+            GOL_HIP(gol::launch_bytes_step(b->cells(b->cur), b->cells(b->cur ^ 1), b->W, b->H,
+                                           b->boundary == GOL_BOUNDED, b->stream));
         return GOL_OK;
     });
+}
+
+// the rule-generic streaming pass: passes of rule_stream_max_k generations (4; "rule_k": up to 8), then the binary
+// remainder
+int run_rule_stream(gol_board* b, int64_t gens) {
+    const int cap = b->opt.rule_k ? b->opt.rule_k : gol::rule_stream_max_k(b->ilv);
+    return ping_pong(b, &b->cur, gens,
+                     [cap](int64_t left) { return (int64_t)gol::rule_stream_largest_k(std::min<int64_t>(left, cap)); },
+                     [&](int64_t g) {
+                         GOL_HIP(gol::launch_rule_stream(b->words(b->cur), b->words(b->cur ^ 1), b->W, b->H, b->pitch,
+                                                         b->ilv, (int)g, b->boundary == GOL_BOUNDED, b->rule,
+                                                         b->opt.rule_seg_rows, b->stream));
+                         return GOL_OK;
+                     });
 }
 
 // Generations of the next streaming pass of a packed board with `left` to go, and that pass
@@ -276,6 +296,7 @@ int step_impl(gol_board* b, int64_t gens) {
         case Pass::Resident: return run_resident(b, gens);
         case Pass::Bytes: return run_bytes(b, gens);
         case Pass::Stream: return run_stream(b, gens);
+        case Pass::RuleStream: return run_rule_stream(b, gens);
         case Pass::None: break;
     }
     return GOL_OK;
@@ -298,6 +319,9 @@ int gol_pass_timing(gol_board* b, int n, double* interior_us, double* wait_us, d
         if (n != parts || !interior_us || !wait_us || !edge_us)
             return fail(GOL_ERR_INVALID, "n must equal gol_num_parts and the arrays must be non-null");
         if (b->multi) return b->multi->timed_pass(interior_us, wait_us, edge_us, &b->generation);
+        if (b->rule_family())
+            return fail(GOL_ERR_UNSUPPORTED, "pass timing measures the B3/S23 streaming pass: this board runs another "
+                                             "rule (gol_set_rule) or the rule family's passes (gol_step_timed times any)");
         if (!b->packed) return fail(GOL_ERR_UNSUPPORTED, "pass timing needs a bit-packed board");
         // a single board's timed pass is one streaming pass: boards whose gol_step takes another pass are refused, so
         // the figure always describes the pass the board runs.  The rows-on-lanes pass only replaces the cooperative

@@ -99,7 +99,10 @@ bool use_resident(const gol_board* b) {
 // as one single-wave launch (board option "wave_resident" = 0 disables it).
 bool use_wave_resident(const gol_board* b) {
     if (!b->opt.wave_resident) return false;
-    return gol::wave_resident_rpl(b->W, b->H) > 0 && (!b->packed || b->ilv == 1);
+    // the rule family's kernels also take rows that do not divide into lanes (gol_wave.hip gol_wave_rule_partial);
+    // a B3/S23 board's choice is what it was
+    const int rpl = b->rule_family() ? gol::wave_rule_rpl(b->W, b->H) : gol::wave_resident_rpl(b->W, b->H);
+    return rpl > 0 && (!b->packed || b->ilv == 1);
 }
 
 // Generations per hand-off of the cooperative pass: the board's "coop_k" option if set, else its temporal-block
@@ -215,9 +218,15 @@ void board_layout(gol_board* b, int nparts, int tblock_k, int ilv) {
 // The pass a gol_step call of `gens` generations takes, first match first (DESIGN.md "Pass order"); the single-wave
 // test comes first and costs a few compares: the 100 x 100 board's call latency is a published number.  A packed board
 // fails the ragged tests, and a byte board the lanes and cooperative ones, on their first compare.
+//
+// A board of the rule family (any rule but B3/S23, or the "rule_table" knob; gol_set_rule refuses multi-part boards)
+// has three passes: the single-wave kernel with the rule table where it applies, the rule-generic streaming pass
+// (gol_rule_step.hip) on every other packed board whatever its layout, and the per-generation byte step under the rule
+// on the byte boards left.  The lanes, cooperative, LDS-resident, ragged and pipelined passes are B3/S23 only.
 PassChoice choose_pass(const gol_board* b, int64_t gens) {
     if (b->multi) return {Pass::Multi, 0};
     if (use_wave_resident(b)) return {Pass::Wave, 0};
+    if (b->rule_family()) return {b->packed ? Pass::RuleStream : Pass::Bytes, 0};
     if (use_lanes(b, gens)) return {Pass::Lanes, 0};
     if (use_coop(b)) return {Pass::Coop, 0};
     int64_t rag_pitch = 0;

@@ -1,0 +1,130 @@
+// gol_rule_plan.h -- the segment and strip plan of the rule-generic streaming pass (gol_rule_step.hip):
+// which wave stores which rows and blocks of a packed board, how many rows and trips it streams, and which row and
+// block every lane loads.  Plain arithmetic: the launcher plans with it, the kernel derives its wave's geometry from the
+// same functions, and tests/cpp/test_rule_plan.cpp walks it alone under the sanitizers.
+//
+//   columns  a row is nblocks interleaved blocks (gol_layout.h).  Strip s stores blocks [62 s, 62 s + 62) of it; its
+//            wave's lane i holds block 62 s - 1 + i, so lanes 0 and 63 are halo and lanes 1..62 store.
+//   rows     segment g stores rows [g seg, g seg + seg) (the last one to H).  Its wave streams the rows from K above
+//            the first to K below the last, seg + 2 K of them, three per loop trip; step t of the stream loads row
+//            r0 - K + t, and the last level's output at step t is row r0 - 2 K + t.
+//   torus    block and row indices are taken modulo nblocks and H (a true modulo: a 3-row board at K = 8 wraps several
+//            times, a row of fewer than 62 blocks repeats across the lanes).
+//   bounded  blocks and rows outside the board are not loaded (they read as zero, and are forced dead at every level).
+//   Steps past the stream (the last trip's tail) and the prefetch past the last trip load nothing.
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define GOL_PLAN_HD __host__ __device__ __forceinline__
+#else
+#define GOL_PLAN_HD static inline
+#endif
+
+namespace gol {
+
+static constexpr int kRuleLanes = 64;
+static constexpr int kRuleStored = kRuleLanes - 2;  // blocks a wave stores per row
+static constexpr int kRuleTripRows = 3;             // rows per loop trip (the 3-row window rotates once per trip)
+static constexpr int kRuleWavesPerBlock = 4;
+
+struct RulePlan {
+    int64_t nblocks;  // blocks per row
+    int64_t H;        // rows of the board
+    int64_t seg;      // rows stored per segment (the last may be shorter)
+    int64_t nstrips, nsegs;
+    int64_t nwaves;   // nstrips * nsegs
+    int32_t K;        // generations of the pass
+    int32_t bounded;
+};
+
+// What one wave does.
+struct RuleWave {
+    int64_t strip, segment;
+    int64_t first_block;  // lane 0's block, 62 strip - 1 (before the modulo)
+    int64_t r0, r1;       // rows [r0, r1) stored
+    int64_t steps;        // rows streamed, r1 - r0 + 2 K
+    int64_t trips;        // loop trips, ceil(steps / 3)
+};
+
+GOL_PLAN_HD int64_t rule_mod(int64_t a, int64_t n) {  // a mod n in [0, n), whatever a's sign
+    const int64_t r = a % n;
+    return r < 0 ? r + n : r;
+}
+
+// seg_opt: 0 = planned (about target_waves waves, segments of at least 2 K rows: at most half of what a wave streams is
+// recomputed), > 0 = that many rows per segment.
+GOL_PLAN_HD RulePlan rule_plan(int64_t nblocks, int64_t H, int K, bool bounded, int64_t seg_opt, int64_t target_waves) {
+    RulePlan p;
+    p.nblocks = nblocks;
+    p.H = H;
+    p.K = K;
+    p.bounded = bounded ? 1 : 0;
+    p.nstrips = (nblocks + kRuleStored - 1) / kRuleStored;
+    int64_t seg;
+    if (seg_opt > 0) {
+        seg = seg_opt;
+    } else {
+        int64_t want = target_waves / p.nstrips;
+        if (want < 1) want = 1;
+        seg = (H + want - 1) / want;
+        if (seg < 2 * (int64_t)K) seg = 2 * (int64_t)K;
+    }
+    if (seg > H) seg = H;
+    p.seg = seg;
+    p.nsegs = (H + seg - 1) / seg;
+    p.nwaves = p.nstrips * p.nsegs;
+    return p;
+}
+
+// Waves that share rows are neighbours: wave = segment * nstrips + strip.
+GOL_PLAN_HD RuleWave rule_wave(const RulePlan& p, int64_t wave) {
+    RuleWave w;
+    w.segment = wave / p.nstrips;
+    w.strip = wave - w.segment * p.nstrips;
+    w.first_block = w.strip * kRuleStored - 1;
+    w.r0 = w.segment * p.seg;
+    w.r1 = w.r0 + p.seg < p.H ? w.r0 + p.seg : p.H;
+    w.steps = w.r1 - w.r0 + 2 * (int64_t)p.K;
+    w.trips = (w.steps + kRuleTripRows - 1) / kRuleTripRows;
+    return w;
+}
+
+// The block lane `lane` loads: false = nothing (it reads as zero), else *block in [0, nblocks).
+GOL_PLAN_HD bool rule_lane_load(const RulePlan& p, const RuleWave& w, int lane, int64_t* block) {
+    const int64_t raw = w.first_block + lane;
+    if (p.bounded) {
+        *block = raw;
+        return raw >= 0 && raw < p.nblocks;
+    }
+    *block = rule_mod(raw, p.nblocks);
+    return true;
+}
+
+// The block lane `lane` stores (rows [r0, r1)): false = none.
+GOL_PLAN_HD bool rule_lane_store(const RulePlan& p, const RuleWave& w, int lane, int64_t* block) {
+    *block = w.first_block + lane;
+    return lane >= 1 && lane <= kRuleStored && *block < p.nblocks;
+}
+
+// The row step t (0 .. 3 trips - 1) loads: false = nothing, else *row in [0, H).
+GOL_PLAN_HD bool rule_step_load(const RulePlan& p, const RuleWave& w, int64_t t, int64_t* row) {
+    const int64_t raw = w.r0 - p.K + t;
+    *row = raw;
+    if (t >= w.steps) return false;  // past the stream
+    if (p.bounded) return raw >= 0 && raw < p.H;
+    *row = rule_mod(raw, p.H);
+    return true;
+}
+
+// The row the last level's output of step t is stored to: false = not stored.
+GOL_PLAN_HD bool rule_step_store(const RulePlan& p, const RuleWave& w, int64_t t, int64_t* row) {
+    *row = w.r0 - 2 * (int64_t)p.K + t;
+    return *row >= w.r0 && *row < w.r1;
+}
+
+GOL_PLAN_HD int64_t rule_stream_grid(const RulePlan& p) {  // workgroups of kRuleWavesPerBlock waves
+    return (p.nwaves + kRuleWavesPerBlock - 1) / kRuleWavesPerBlock;
+}
+
+}  // namespace gol

@@ -125,17 +125,19 @@ def run(
     num_gpus: int = 1,
     view=None,
     view_mode: int = VIEW_ANY,
+    rule="B3/S23",
 ) -> GameOfLife:
     """GameOfLifeDriver.fs:13-41.  ``seed`` replaces ``int DateTime.Now.Ticks`` (L10) so runs are
     reproducible; the board is seeded x outer / y inner with ``Random.Next() % 2 = 0`` (L9-11,16-19).
     With ``period_s`` a timer ticks like L38-40 (reference: ProcessorCount * 70 ms).  ``num_gpus`` > 1
     spreads the board over that many GPUs of this process (row strips; needs a width divisible by 32).
     ``emit="view"`` posts one ``Board.render_view`` frame per tick for ``view = (x, y, scale, out_w, out_h)`` in
-    ``view_mode`` (VIEW_ANY / VIEW_DENSITY) instead of the whole board."""
+    ``view_mode`` (VIEW_ANY / VIEW_DENSITY) instead of the whole board.  ``rule``: the life-like rule every tick runs
+    under, as ``Board.set_rule`` takes it (the reference's is B3/S23)."""
     if seed is None:
         seed = int(time.time_ns() // 100) & 0xFFFFFFFF  # .NET ticks are 100 ns; `int` truncates to 32 bits
         seed = seed - (1 << 32) if seed >= (1 << 31) else seed
-    board = Board(g.Width, g.Height, boundary, tblock_k, num_gpus=num_gpus)
+    board = Board(g.Width, g.Height, boundary, tblock_k, num_gpus=num_gpus, rule=rule)
     board.seed_dotnet(seed, INIT_DOTNET_MOD2)
     try:
         game = GameOfLife(board, agent or UpdateAgent(g), emit, view, view_mode)

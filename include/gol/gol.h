@@ -308,13 +308,24 @@ int gol_batch_synchronize(gol_batch* b);
  *     gol_batch_step, gol_batch_step_timed, gol_batch_step_trace and gol_ensemble_cycles.
  *   Boundaries: on a bounded board the cells outside are dead forever and are no cells of the board, also under a rule
  *     with B0; on a torus every cell has 8 neighbours (on a 3-wide or 3-high torus the other cells of the 3-line).
- * The gol_board handle is B3/S23 only. */
+ *   gol_set_rule / gol_rule  the same for a single board (gol_board), masks as gol_rule_parse gives them.  A new board
+ *     is B3/S23.  Masks outside 0..0x1FF and null outputs are GOL_ERR_INVALID with the board's rule as it was.  The
+ *     rule is a property of the handle, not of the cells: gol_clear, gol_set_cells, the seeds, gol_load_packed and
+ *     gol_place_rle leave it alone, and snapshots (gol_save_packed, the snapshot files) do not carry it -- whoever
+ *     restores a snapshot sets the rule again.  It is the rule of gol_step and gol_step_timed; gol_pass_timing times the
+ *     B3/S23 streaming pass and returns GOL_ERR_UNSUPPORTED under any other rule.  Under B3/S23 a board takes exactly
+ *     the passes it always took; under another rule a board up to 128 x 256 (any height up to 256) runs the single-wave pass
+ *     with the rule table, every other bit-packed board the rule-generic streaming pass (csrc/gol_rule_step.hip: 4 generations per
+ *     pass over the board, any size, any layout) and the remaining byte boards one launch per generation (DESIGN.md
+ *     4.12).  A board on several GPUs accepts B3/S23 only: any other rule is GOL_ERR_UNSUPPORTED, rule unchanged. */
 #define GOL_RULE_LIFE_BIRTH 0x008
 #define GOL_RULE_LIFE_SURVIVE 0x00C
 int gol_rule_parse(const char* text, int* birth, int* survive);
 int gol_rule_format(int birth, int survive, char* out, int64_t len);
 int gol_ensemble_set_rule(gol_batch* b, int birth, int survive);
 int gol_ensemble_rule(gol_batch* b, int* birth, int* survive);
+int gol_set_rule(gol_board* b, int birth, int survive);
+int gol_rule(gol_board* b, int* birth, int* survive);
 /* The ensemble's cycle census: for every board, after how many generations it enters a cycle and of
  * what period, one launch, one wavefront per board, the search in that wave's registers.
  *   Definition: B_0 = board i's current cells, B_(t+1) = the next generation of B_t under the batch's rule and boundary;

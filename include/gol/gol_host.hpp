@@ -212,6 +212,24 @@ class Board {
         check(gol_place_rle(b_, rle.c_str(), x, y), "gol_place_rle");
         return *this;
     }
+    // The rule of every later step ("B36/S23", "S23/B36", "23/36"; B3/S23 until set).  A property of the handle: the
+    // setters and snapshots neither change nor carry it.  Boards on several GPUs take B3/S23 only.
+    Board& setRule(const std::string& rule) {
+        int birth = 0, survive = 0;
+        check(gol_rule_parse(rule.c_str(), &birth, &survive), "gol_rule_parse");
+        return setRule(birth, survive);
+    }
+    Board& setRule(int birth, int survive) {  // 9-bit masks, bit n = n live neighbours
+        check(gol_set_rule(b_, birth, survive), "gol_set_rule");
+        return *this;
+    }
+    std::string rule() const {  // canonical: "B36/S23"
+        int birth = 0, survive = 0;
+        char text[22];
+        check(gol_rule(b_, &birth, &survive), "gol_rule");
+        check(gol_rule_format(birth, survive, text, sizeof text), "gol_rule_format");
+        return text;
+    }
     Board& step(int64_t generations = 1) {
         check(gol_step(b_, generations), "gol_step");
         return *this;

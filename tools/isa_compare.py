@@ -1,0 +1,84 @@
+#!/usr/bin/env python
+"""Compare every kernel's instruction stream between two trees of csrc/ (the parent's and this one's): cross-compile each
+.hip file of both to gfx950 assembly, renumber the labels of each kernel in order of appearance, and compare kernel by
+kernel.  Template arguments that only a later revision has (an empty trailing parameter pack) are dropped from the name
+before matching, so a kernel that gained an empty pack still meets its parent.
+
+    python tools/isa_compare.py <parent csrc dir> <this csrc dir> file.hip [file.hip ...]
+"""
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def assembly(csrc, name, out):
+    inc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(csrc))), "include")
+    if not os.path.isdir(inc):
+        inc = os.path.join(ROOT, "include")
+    subprocess.run([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "--offload-arch=gfx950", "-O3", "-std=c++17", "-x", "hip", "--cuda-device-only",
+                    "-S", "-I", inc, "-I", csrc, os.path.join(csrc, name), "-o", out], check=True,
+                   stderr=subprocess.DEVNULL)
+    return open(out).read()
+
+
+def demangle(names):
+    out = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True,
+                         check=True).stdout.split("\n")
+    return dict(zip(names, out))
+
+
+def kernels(text):
+    """{demangled name: [instruction lines, labels renumbered]} of every .amdhsa_kernel of the file."""
+    wanted = set(re.findall(r"\.amdhsa_kernel\s+(\S+)", text))
+    body, cur = {}, None
+    for line in text.splitlines():
+        m = re.match(r"^(\S+):\s*(;.*)?$", line)
+        if m and m.group(1) in wanted:
+            cur = m.group(1)
+            body[cur] = []
+            continue
+        if cur is None:
+            continue
+        s = line.split(";")[0].strip()
+        if s.startswith(".Lfunc_end"):
+            cur = None
+            continue
+        if not s or (s.startswith(".") and not re.match(r"^\.LBB\d+_\d+:", s)):
+            continue
+        body[cur].append(s)
+    names = demangle(sorted(body))
+    out = {}
+    for sym, lines in body.items():
+        seen = {}
+        def ren(m):
+            return seen.setdefault(m.group(0), f".L{len(seen)}")
+        out[re.sub(r",\s*>", ">", re.sub(r"\s+", " ", names[sym]))] = [re.sub(r"\.LBB\d+_\d+", ren, l) for l in lines]
+    return out
+
+
+def main():
+    parent, this, files = sys.argv[1], sys.argv[2], sys.argv[3:]
+    bad = 0
+    with tempfile.TemporaryDirectory() as d:
+        for f in files:
+            a = kernels(assembly(parent, f, os.path.join(d, "a.s")))
+            b = kernels(assembly(this, f, os.path.join(d, "b.s")))
+            same = [k for k in a if k in b and a[k] == b[k]]
+            diff = [k for k in a if k in b and a[k] != b[k]]
+            gone = [k for k in a if k not in b]
+            new = [k for k in b if k not in a]
+            print(f"{f}: {len(a)} kernels in the parent, {len(same)} identical, {len(diff)} differ, {len(gone)} missing, "
+                  f"{len(new)} new")
+            for k in diff + gone:
+                print("   ", "DIFFERS" if k in diff else "MISSING", k)
+            bad += len(diff) + len(gone)
+    print("all parent kernels identical" if not bad else f"{bad} parent kernels differ or are missing")
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
