@@ -109,6 +109,12 @@ extern int gol_rule_format(int birth, int survive, byte[] out, int64 len)   // l
 extern int gol_ensemble_set_rule(nativeint batch, int birth, int survive)
 [<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
 extern int gol_ensemble_rule(nativeint batch, int& birth, int& survive)
+// ... one rule per board (n = count entries each): board i runs under (birth[i], survive[i]); gol_ensemble_rules
+// returns the table, or count copies of the one rule, and either of its arrays may be null
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int gol_ensemble_set_rules(nativeint batch, int[] birth, int[] survive, int64 n)
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int gol_ensemble_rules(nativeint batch, int[] birth, int[] survive, int64 n)
 // ... and of a single board (B3/S23 until set; boards on several GPUs take B3/S23 only)
 [<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
 extern int gol_set_rule(nativeint board, int birth, int survive)

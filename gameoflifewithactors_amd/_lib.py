@@ -179,6 +179,9 @@ SIGNATURES = {
     "gol_rule_format": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_char_p, i64]),
     "gol_ensemble_set_rule": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int]),
     "gol_ensemble_rule": (ctypes.c_int, [vp, ip, ip]),
+    # ... one rule per board of the batch (count entries each)
+    "gol_ensemble_set_rules": (ctypes.c_int, [vp, ip, ip, i64]),
+    "gol_ensemble_rules": (ctypes.c_int, [vp, ip, ip, i64]),
     # ... and of a single board
     "gol_set_rule": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int]),
     "gol_rule": (ctypes.c_int, [vp, ip, ip]),

@@ -10,7 +10,8 @@ other question asked of an ensemble of soups -- after how many generations does 
 what period -- in one launch too: each wave runs the cycle search on the board in its registers
 (``csrc/gol_cycles.hip``), where ``step(1)`` + ``hashes()`` per generation would be thousands of launches
 and readbacks.  All of it runs under the batch's rule: B3/S23 unless ``rule=`` / ``set_rule`` names another life-like
-rule ("B36/S23", "B3678/S34678", ...).
+rule ("B36/S23", "B3678/S34678", ...) -- or under one rule per board (``set_rules``):
+one soup under thousands of rules is one launch as well.
 """
 from __future__ import annotations
 
@@ -126,10 +127,42 @@ class BoardBatch:
 
     @property
     def rule(self) -> str:
-        """The batch's rule in canonical form, "B3/S23" for a new batch."""
+        """The batch's rule in canonical form, "B3/S23" for a new batch.  After ``set_rules`` it is the rule all boards
+        agree on; where they differ it raises NotImplementedError (``rules`` has the list)."""
         b, s = ctypes.c_int(), ctypes.c_int()
         check(self._lib.gol_ensemble_rule(self._h, ctypes.byref(b), ctypes.byref(s)), "gol_ensemble_rule")
         return _lib.rule_format(b.value, s.value)
+
+    def set_rules(self, rules) -> "BoardBatch":
+        """One rule per board: board i runs every later ``step``, ``step_timed``, ``step_trace`` and ``cycles`` under
+        ``rules[i]``.  ``rules`` is a sequence of ``count`` strings or ``(birth, survive)`` pairs as ``set_rule`` takes
+        them, or an ``(count, 2)`` integer array of masks.  The table is checked as a whole before any of it is used: a
+        wrong length or a mask outside 0..0x1FF raises ValueError and leaves the batch's rules as they were.  Like
+        ``set_rule`` it changes only the future, and ``set_cells``, the seeds and ``clear`` keep it; a later
+        ``set_rule`` puts the batch back under one rule."""
+        if isinstance(rules, np.ndarray):
+            a = rules
+        else:
+            a = np.array([_lib.rule_parse(r) if isinstance(r, (str, bytes)) else (int(r[0]), int(r[1]))
+                          for r in rules], dtype=np.int64).reshape(-1, 2)
+        if a.dtype.kind not in "iu" or a.ndim != 2 or a.shape[1] != 2:
+            raise ValueError(f"rules must be (n, 2) integer masks, got {a.dtype} {a.shape}")
+        if a.size and (a.min() < -2**31 or a.max() >= 2**31):
+            raise ValueError("birth and survive masks must lie in 0..0x1FF")
+        birth, survive = (np.ascontiguousarray(a[:, k], dtype=np.intc) for k in (0, 1))
+        check(self._lib.gol_ensemble_set_rules(self._h, birth.ctypes.data_as(_lib.ip), survive.ctypes.data_as(_lib.ip),
+                                               a.shape[0]), "gol_ensemble_set_rules")
+        return self
+
+    @property
+    def rules(self) -> list:
+        """Every board's rule in canonical form: the table of ``set_rules``, or ``count`` times the batch's one rule."""
+        birth, survive = (np.empty(self.count, dtype=np.intc) for _ in range(2))
+        check(self._lib.gol_ensemble_rules(self._h, birth.ctypes.data_as(_lib.ip), survive.ctypes.data_as(_lib.ip),
+                                           self.count), "gol_ensemble_rules")
+        pairs = list(zip(birth.tolist(), survive.tolist()))
+        text = {k: _lib.rule_format(*k) for k in set(pairs)}  # a table names few distinct rules, 2^18 at the most
+        return [text[k] for k in pairs]
 
     # ---------------------------------------------------------------- stepping
     def step(self, generations: int = 1) -> "BoardBatch":

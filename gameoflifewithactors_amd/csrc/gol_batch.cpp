@@ -29,12 +29,18 @@ struct gol_batch {
     int32_t* cycles = nullptr;  // count * 4 result words of gol_ensemble_cycles, allocated by its first call
     int64_t generation = 0;
     uint32_t rule = gol::kRuleLifePacked;  // birth | survive << 9 (gol_ensemble_set_rule)
+    // gol_ensemble_set_rules: one packed rule per board.  rules_host non-empty = per-board mode: the device table
+    // `rules` (count words, allocated by the first call, kept until destroy) is the launches' rule source and `rule`
+    // is unused; gol_ensemble_set_rule empties rules_host and the batch runs under `rule` again.
+    uint32_t* rules = nullptr;
+    std::vector<uint32_t> rules_host;
     bool rule_table = false;  // B3/S23 through the rule-table kernels too (gol_debug_batch_rule_table)
     double cycles_us = -1;  // device time of the last census launch (gol_debug_ensemble_cycles_us)
 
     int64_t cells() const { return W * H; }
     int64_t board_words() const { return H * nw; }
     uint32_t* board(int64_t i) { return words + i * board_words(); }
+    const uint32_t* table() const { return rules_host.empty() ? nullptr : rules; }  // the launchers' `rules`
 };
 
 namespace {
@@ -54,6 +60,7 @@ int with_batch(gol_batch* b, F&& f) {
 void free_batch(gol_batch* b) {
     if (b->words) (void)hipFree(b->words);
     if (b->cycles) (void)hipFree(b->cycles);
+    if (b->rules) (void)hipFree(b->rules);
     if (b->stream) (void)hipStreamDestroy(b->stream);
     delete b;
 }
@@ -225,7 +232,7 @@ int gol_batch_step(gol_batch* b, int64_t generations) {
         if (generations < 0) return fail(GOL_ERR_INVALID, "generations must be >= 0");
         if (generations == 0) return GOL_OK;
         GOL_HIP(gol::launch_batch_step(b->words, b->count, b->W, b->H, b->boundary == GOL_BOUNDED, 1, generations,
-                                       nullptr, b->group_waves, b->rule, b->rule_table, b->stream));
+                                       nullptr, b->group_waves, b->rule, b->rule_table, b->table(), b->stream));
         b->generation += generations;
         return GOL_OK;
     });
@@ -240,7 +247,7 @@ int gol_batch_step_timed(gol_batch* b, int64_t generations, double* elapsed_us) 
         GOL_HIP(hipEventRecord(ev.e0, b->stream));
         if (generations > 0)
             GOL_HIP(gol::launch_batch_step(b->words, b->count, b->W, b->H, b->boundary == GOL_BOUNDED, 1, generations,
-                                           nullptr, b->group_waves, b->rule, b->rule_table, b->stream));
+                                           nullptr, b->group_waves, b->rule, b->rule_table, b->table(), b->stream));
         GOL_HIP(hipEventRecord(ev.e1, b->stream));
         b->generation += generations;
         return ev.elapsed_us(elapsed_us);
@@ -258,7 +265,8 @@ int gol_batch_step_trace(gol_batch* b, int64_t generations, int64_t every, uint3
         const size_t bytes = (size_t)len * sizeof(uint32_t);
         GOL_RC(dev.alloc(bytes, "trace"));
         GOL_HIP(gol::launch_batch_step(b->words, b->count, b->W, b->H, b->boundary == GOL_BOUNDED, samples, every,
-                                       dev.as<uint32_t>(), b->group_waves, b->rule, b->rule_table, b->stream));
+                                       dev.as<uint32_t>(), b->group_waves, b->rule, b->rule_table, b->table(),
+                                       b->stream));
         b->generation += generations;
         GOL_HIP(hipMemcpyAsync(trace, dev.p, bytes, hipMemcpyDeviceToHost, b->stream));
         GOL_HIP(hipStreamSynchronize(b->stream));
@@ -330,7 +338,7 @@ int gol_ensemble_cycles(gol_batch* b, int64_t max_generations, int64_t* transien
         GOL_RC(ev.create());
         GOL_HIP(hipEventRecord(ev.e0, b->stream));
         GOL_HIP(gol::launch_batch_cycles(b->words, b->count, b->W, b->H, b->boundary == GOL_BOUNDED, max_generations,
-                                         b->cycles, b->rule, b->rule_table, b->stream));
+                                         b->cycles, b->rule, b->rule_table, b->table(), b->stream));
         GOL_HIP(hipEventRecord(ev.e1, b->stream));
         GOL_HIP(hipMemcpyAsync(host.data(), b->cycles, bytes, hipMemcpyDeviceToHost, b->stream));
         GOL_HIP(hipStreamSynchronize(b->stream));
@@ -361,6 +369,7 @@ int gol_ensemble_set_rule(gol_batch* b, int birth, int survive) {
         if (!gol::rule_masks_ok(birth, survive))
             return fail(GOL_ERR_INVALID, "birth and survive masks must lie in 0..0x1FF");
         b->rule = gol::rule_pack(birth, survive);
+        b->rules_host.clear();  // one rule for every board again: the kernels and arguments of a batch without a table
         return GOL_OK;
     });
 }
@@ -368,8 +377,48 @@ int gol_ensemble_set_rule(gol_batch* b, int birth, int survive) {
 int gol_ensemble_rule(gol_batch* b, int* birth, int* survive) {
     if (!b) return fail(GOL_ERR_INVALID, "null batch");
     std::lock_guard<std::mutex> g(b->mu);
-    if (birth) *birth = (int)(b->rule & gol::kRuleMaskMax);
-    if (survive) *survive = (int)(b->rule >> 9);
+    uint32_t rule = b->rule;
+    if (!b->rules_host.empty() && !gol::batch_rules_common(b->rules_host.data(), b->count, &rule))
+        return fail(GOL_ERR_UNSUPPORTED, "the boards of this batch run under different rules: gol_ensemble_rules "
+                                         "returns the table");
+    if (birth) *birth = (int)(rule & gol::kRuleMaskMax);
+    if (survive) *survive = (int)(rule >> 9);
+    return GOL_OK;
+}
+
+int gol_ensemble_set_rules(gol_batch* b, const int* birth, const int* survive, int64_t n) {
+    return with_batch(b, [&] {
+        // the whole table is judged and packed before the device hears of it: a refusal leaves the rules as they were
+        const char* why = "";
+        int64_t bad = -1;
+        std::vector<uint32_t> packed((size_t)b->count);
+        if (!gol::batch_rules_pack(birth, survive, n, b->count, packed.data(), &why, &bad))
+            return fail(GOL_ERR_INVALID, bad < 0 ? std::string(why) : why + (" (board " + std::to_string(bad) + ")"));
+        const size_t bytes = (size_t)b->count * sizeof(uint32_t);
+        if (!b->rules) {
+            const hipError_t e = hipMalloc(reinterpret_cast<void**>(&b->rules), bytes);
+            if (e != hipSuccess) {
+                b->rules = nullptr;
+                return fail(GOL_ERR_OOM, std::string("hipMalloc rule table: ") + hipGetErrorString(e));
+            }
+        }
+        // on the batch's stream: after every step launched so far, before every later one
+        GOL_HIP(hipMemcpyAsync(b->rules, packed.data(), bytes, hipMemcpyHostToDevice, b->stream));
+        GOL_HIP(hipStreamSynchronize(b->stream));  // `packed` is borrowed by the copy
+        b->rules_host.swap(packed);
+        return GOL_OK;
+    });
+}
+
+int gol_ensemble_rules(gol_batch* b, int* birth, int* survive, int64_t n) {
+    if (!b) return fail(GOL_ERR_INVALID, "null batch");
+    std::lock_guard<std::mutex> g(b->mu);
+    if (n != b->count) return fail(GOL_ERR_INVALID, "birth and survive hold count entries");
+    for (int64_t i = 0; i < n; i++) {
+        const uint32_t rule = b->rules_host.empty() ? b->rule : b->rules_host[(size_t)i];
+        if (birth) birth[i] = (int)(rule & gol::kRuleMaskMax);
+        if (survive) survive[i] = (int)(rule >> 9);
+    }
     return GOL_OK;
 }
 

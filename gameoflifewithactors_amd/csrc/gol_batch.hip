@@ -22,18 +22,21 @@ namespace {
 // generations the board's population goes to trace[t * count + board] (t = 0 .. samples - 1); otherwise samples is 1
 // and trace unused.  A wave past the last board leaves before it touches memory.
 //
-// PackedRule is empty or one uint32_t.  Empty: B3/S23 by life_next, the kernel and its arguments as they were before
-// rules existed.  One word: any life-like rule by its packed masks (gol_wave_body.h wave_rule).  launch_batch_step
-// picks the family; nothing else lets a rule change what runs.
+// PackedRule is empty, one uint32_t or one const uint32_t*.  Empty: B3/S23 by life_next, the kernel and its arguments
+// as they were before rules existed.  One word: any life-like rule by its packed masks (gol_wave_body.h board_rule).
+// A pointer: `count` packed rules, one per board (gol_ensemble_set_rules); the wave reads its own once, as a scalar,
+// after the test that sends a wave past the last board away and before it loads its board, so the waves of one
+// workgroup may run different rules: each takes its own scalar branches in rule_next_row.  launch_batch_step picks the
+// family; nothing else lets a rule change what runs.
 template <int NW, int RPL, bool BOUNDED, bool TRACE, class... PackedRule>
 __global__ __launch_bounds__(256) void gol_batch_step(uint32_t* __restrict__ words, int64_t count, int W, int H,
                                                       int samples, int64_t every, uint32_t* __restrict__ trace,
                                                       PackedRule... packed_rule) {
-    const auto rule = wave_rule(packed_rule...);
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t board = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave;
     if (board >= count) return;
+    const auto rule = board_rule(board, packed_rule...);
     const int nl = H / RPL;  // active lanes
     const bool active = lane < nl;
     uint32_t* rows = words + (board * H + lane * RPL) * NW;  // this lane's RPL * NW words
@@ -157,10 +160,14 @@ unsigned blocks(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
 template <int NW, int RPL>
 hipError_t step_nr(uint32_t* words, int64_t count, int W, int H, bool bounded, int samples, int64_t every,
-                   uint32_t* trace, int group_waves, bool table, uint32_t rule, hipStream_t s) {
+                   uint32_t* trace, int group_waves, bool table, uint32_t rule, const uint32_t* rules,
+                   hipStream_t s) {
     const dim3 grid(blocks(count, group_waves)), block(64 * group_waves);
 #define GOL_BATCH_LAUNCH(B, T)                                                                                        \
-    if (table)                                                                                                        \
+    if (rules)                                                                                                        \
+        hipLaunchKernelGGL((gol_batch_step<NW, RPL, B, T, const uint32_t*>), grid, block, 0, s, words, count, W, H,   \
+                           samples, every, trace, rules);                                                             \
+    else if (table)                                                                                                   \
         hipLaunchKernelGGL((gol_batch_step<NW, RPL, B, T, uint32_t>), grid, block, 0, s, words, count, W, H, samples,      \
                            every, trace, rule);                                                                       \
     else                                                                                                              \
@@ -185,16 +192,17 @@ hipError_t step_nr(uint32_t* words, int64_t count, int W, int H, bool bounded, i
 
 template <int NW>
 hipError_t step_n(uint32_t* words, int64_t count, int W, int H, bool bounded, int samples, int64_t every,
-                  uint32_t* trace, int group_waves, int rpl, bool table, uint32_t rule, hipStream_t s) {
+                  uint32_t* trace, int group_waves, int rpl, bool table, uint32_t rule, const uint32_t* rules,
+                  hipStream_t s) {
     switch (rpl) {
         case 1: return step_nr<NW, 1>(words, count, W, H, bounded, samples, every, trace, group_waves, table, rule,
-                                          s);
+                                          rules, s);
         case 2: return step_nr<NW, 2>(words, count, W, H, bounded, samples, every, trace, group_waves, table, rule,
-                                          s);
+                                          rules, s);
         case 3: return step_nr<NW, 3>(words, count, W, H, bounded, samples, every, trace, group_waves, table, rule,
-                                          s);
+                                          rules, s);
         case 4: return step_nr<NW, 4>(words, count, W, H, bounded, samples, every, trace, group_waves, table, rule,
-                                          s);
+                                          rules, s);
     }
     return hipErrorInvalidValue;
 }
@@ -203,7 +211,7 @@ hipError_t step_n(uint32_t* words, int64_t count, int W, int H, bool bounded, in
 
 hipError_t launch_batch_step(uint32_t* words, int64_t count, int64_t W, int64_t H, bool bounded, int64_t samples,
                              int64_t every, uint32_t* trace, int group_waves, uint32_t rule, bool force_table,
-                             hipStream_t s) {
+                             const uint32_t* rules, hipStream_t s) {
     const int rpl = wave_resident_rpl(W, H);
     const bool table = force_table || rule != kRuleLifePacked;  // B3/S23 runs the code it always ran
     if (!rpl || rule >= (1u << 18) || count < 1 || count > kBatchCountMax || samples < 1 || samples > INT32_MAX || every < 1 ||
@@ -212,16 +220,16 @@ hipError_t launch_batch_step(uint32_t* words, int64_t count, int64_t W, int64_t 
     switch ((int)((W + 31) / 32)) {
         case 1:
             return step_n<1>(words, count, (int)W, (int)H, bounded, (int)samples, every, trace, group_waves, rpl, table,
-                             rule, s);
+                             rule, rules, s);
         case 2:
             return step_n<2>(words, count, (int)W, (int)H, bounded, (int)samples, every, trace, group_waves, rpl, table,
-                             rule, s);
+                             rule, rules, s);
         case 3:
             return step_n<3>(words, count, (int)W, (int)H, bounded, (int)samples, every, trace, group_waves, rpl, table,
-                             rule, s);
+                             rule, rules, s);
         case 4:
             return step_n<4>(words, count, (int)W, (int)H, bounded, (int)samples, every, trace, group_waves, rpl, table,
-                             rule, s);
+                             rule, rules, s);
     }
     return hipErrorInvalidValue;
 }

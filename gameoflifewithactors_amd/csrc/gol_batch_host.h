@@ -1,9 +1,10 @@
-// gol_batch_host.h -- the host-only arithmetic of the batch handle (gol_batch.cpp): argument ranges and the .NET
-// seeding of packed boards.  No HIP here, so tests/cpp/test_batch_host.cpp compiles it alone under the address and
-// undefined-behaviour sanitizers.
+// gol_batch_host.h -- the host-only arithmetic of the batch handle (gol_batch.cpp): argument ranges, the .NET seeding
+// of packed boards and the per-board rule table.  No HIP here, so tests/cpp/test_batch_host.cpp and
+// tests/cpp/test_batch_rules_host.cpp compile it alone under the address and undefined-behaviour sanitizers.
 #pragma once
 #include <stdint.h>
 
+#include "gol_rule.h"
 #include "gol_seed_rle.h"
 
 namespace gol {
@@ -37,6 +38,33 @@ inline bool batch_trace_ok(int64_t generations, int64_t every, int64_t count, in
     if (t > kBatchTraceMax / count) return *why = "more than 2^26 trace entries", false;
     if (len != t * count) return *why = "trace length must be (generations / every) * count", false;
     *samples = t;
+    return true;
+}
+
+// A per-board rule table (gol_ensemble_set_rules): n == count entries, both arrays there, every mask in 0..0x1FF.  The
+// whole table is judged before a word of `packed` is written: true with packed[i] = rule_pack(birth[i], survive[i])
+// for i in [0, count), or false with *why set and `packed` untouched.  *bad_index, when given, is the first entry
+// with a mask out of range, or -1.
+inline bool batch_rules_pack(const int* birth, const int* survive, int64_t n, int64_t count, uint32_t* packed,
+                             const char** why, int64_t* bad_index = nullptr) {
+    if (bad_index) *bad_index = -1;
+    if (!birth || !survive) return *why = "birth and survive must hold count entries: null array", false;
+    if (n != count) return *why = "birth and survive must hold count entries", false;
+    if (!packed) return *why = "null table", false;
+    for (int64_t i = 0; i < n; i++)
+        if (!rule_masks_ok(birth[i], survive[i])) {
+            if (bad_index) *bad_index = i;
+            return *why = "birth and survive masks must lie in 0..0x1FF", false;
+        }
+    for (int64_t i = 0; i < n; i++) packed[i] = rule_pack(birth[i], survive[i]);
+    return true;
+}
+
+// The rule every entry of a packed table agrees on (count >= 1): true with *rule set, or false with *rule untouched.
+inline bool batch_rules_common(const uint32_t* packed, int64_t count, uint32_t* rule) {
+    for (int64_t i = 1; i < count; i++)
+        if (packed[i] != packed[0]) return false;
+    *rule = packed[0];
     return true;
 }
 

@@ -43,22 +43,23 @@ struct WaveBoard {
 };
 
 // Board blockIdx.x: out[4 board ..] = transient, period, population of B_transient, generation steps run.
-// PackedRule is empty (B3/S23 by life_next: the kernel as it was before rules existed) or one uint32_t (any life-like
-// rule by its packed masks), as in gol_batch.hip: launch_batch_cycles picks.
+// PackedRule is empty (B3/S23 by life_next: the kernel as it was before rules existed), one uint32_t (any life-like
+// rule by its packed masks) or one const uint32_t* (`count` packed rules, the wave's own read once as a scalar after
+// the test on `board`), as in gol_batch.hip: launch_batch_cycles picks.
 template <int NW, int RPL, bool BOUNDED, class... PackedRule>
 __global__ __launch_bounds__(64) void gol_batch_cycles(const uint32_t* __restrict__ words, int64_t count, int W, int H,
                                                        int max_generations, int32_t* __restrict__ out,
                                                        PackedRule... packed_rule) {
-    using Rule = decltype(wave_rule(packed_rule...));
     const int lane = threadIdx.x;
     const int64_t board = blockIdx.x;
     if (board >= count) return;
+    using Rule = decltype(board_rule(board, packed_rule...));
     const int nl = H / RPL;  // active lanes
     const bool active = lane < nl;
     const uint32_t* rows = words + (board * H + lane * RPL) * NW;  // this lane's RPL * NW words
     CycleWave<Rule> cw;
     cw.geom = wave_geom<BOUNDED>(W, nl, lane);
-    cw.rule = wave_rule(packed_rule...);
+    cw.rule = board_rule(board, packed_rule...);
     cw.lanes = __ballot(active);
     using Board = WaveBoard<NW, RPL, BOUNDED, Rule>;
     const auto load = [&]() {
@@ -96,9 +97,16 @@ __global__ __launch_bounds__(64) void gol_batch_cycles(const uint32_t* __restric
 
 template <int NW, int RPL>
 hipError_t cycles_nr(const uint32_t* words, int64_t count, int W, int H, bool bounded, int G, int32_t* out, bool table,
-                     uint32_t rule, hipStream_t s) {
+                     uint32_t rule, const uint32_t* rules, hipStream_t s) {
     const dim3 grid((unsigned)count), block(64);  // count <= 2^22
-    if (table) {
+    if (rules) {
+        if (bounded)
+            hipLaunchKernelGGL((gol_batch_cycles<NW, RPL, true, const uint32_t*>), grid, block, 0, s, words, count, W,
+                               H, G, out, rules);
+        else
+            hipLaunchKernelGGL((gol_batch_cycles<NW, RPL, false, const uint32_t*>), grid, block, 0, s, words, count, W,
+                               H, G, out, rules);
+    } else if (table) {
         if (bounded)
             hipLaunchKernelGGL((gol_batch_cycles<NW, RPL, true, uint32_t>), grid, block, 0, s, words, count, W, H, G, out,
                                rule);
@@ -114,12 +122,12 @@ hipError_t cycles_nr(const uint32_t* words, int64_t count, int W, int H, bool bo
 
 template <int NW>
 hipError_t cycles_n(const uint32_t* words, int64_t count, int W, int H, bool bounded, int G, int32_t* out, int rpl,
-                    bool table, uint32_t rule, hipStream_t s) {
+                    bool table, uint32_t rule, const uint32_t* rules, hipStream_t s) {
     switch (rpl) {
-        case 1: return cycles_nr<NW, 1>(words, count, W, H, bounded, G, out, table, rule, s);
-        case 2: return cycles_nr<NW, 2>(words, count, W, H, bounded, G, out, table, rule, s);
-        case 3: return cycles_nr<NW, 3>(words, count, W, H, bounded, G, out, table, rule, s);
-        case 4: return cycles_nr<NW, 4>(words, count, W, H, bounded, G, out, table, rule, s);
+        case 1: return cycles_nr<NW, 1>(words, count, W, H, bounded, G, out, table, rule, rules, s);
+        case 2: return cycles_nr<NW, 2>(words, count, W, H, bounded, G, out, table, rule, rules, s);
+        case 3: return cycles_nr<NW, 3>(words, count, W, H, bounded, G, out, table, rule, rules, s);
+        case 4: return cycles_nr<NW, 4>(words, count, W, H, bounded, G, out, table, rule, rules, s);
     }
     return hipErrorInvalidValue;
 }
@@ -128,7 +136,7 @@ hipError_t cycles_n(const uint32_t* words, int64_t count, int W, int H, bool bou
 
 hipError_t launch_batch_cycles(const uint32_t* words, int64_t count, int64_t W, int64_t H, bool bounded,
                                int64_t max_generations, int32_t* out, uint32_t rule, bool force_table,
-                               hipStream_t s) {
+                               const uint32_t* rules, hipStream_t s) {
     const int rpl = wave_resident_rpl(W, H);
     const bool table = force_table || rule != kRuleLifePacked;  // B3/S23 runs the code it always ran
     if (!rpl || rule >= (1u << 18) || !words || !out || count < 1 || count > kBatchCountMax || max_generations < 1 ||
@@ -136,10 +144,10 @@ hipError_t launch_batch_cycles(const uint32_t* words, int64_t count, int64_t W, 
         return hipErrorInvalidValue;
     const int G = (int)max_generations;
     switch ((int)((W + 31) / 32)) {
-        case 1: return cycles_n<1>(words, count, (int)W, (int)H, bounded, G, out, rpl, table, rule, s);
-        case 2: return cycles_n<2>(words, count, (int)W, (int)H, bounded, G, out, rpl, table, rule, s);
-        case 3: return cycles_n<3>(words, count, (int)W, (int)H, bounded, G, out, rpl, table, rule, s);
-        case 4: return cycles_n<4>(words, count, (int)W, (int)H, bounded, G, out, rpl, table, rule, s);
+        case 1: return cycles_n<1>(words, count, (int)W, (int)H, bounded, G, out, rpl, table, rule, rules, s);
+        case 2: return cycles_n<2>(words, count, (int)W, (int)H, bounded, G, out, rpl, table, rule, rules, s);
+        case 3: return cycles_n<3>(words, count, (int)W, (int)H, bounded, G, out, rpl, table, rule, rules, s);
+        case 4: return cycles_n<4>(words, count, (int)W, (int)H, bounded, G, out, rpl, table, rule, rules, s);
     }
     return hipErrorInvalidValue;
 }

@@ -261,10 +261,12 @@ hipError_t launch_wave_resident(const void* src, void* dst, int64_t W, int64_t H
 // samples x every generations of every board, in place.  trace == nullptr: samples must be 1; otherwise
 // trace[t * count + i] = population of board i after (t + 1) * every generations.  group_waves: boards (waves) per
 // workgroup, 1 or 4.  rule: the packed masks (gol_rule.h rule_pack); B3/S23 runs the life_next instantiations, any
-// other rule -- or B3/S23 with force_table (gol_debug_batch_rule_table) -- the rule-table family.
+// other rule -- or B3/S23 with force_table (gol_debug_batch_rule_table) -- the rule-table family.  rules: nullptr, or
+// `count` packed rules on the device, board i's at rules[i] (gol_ensemble_set_rules): then the per-board family runs
+// and `rule` / force_table choose nothing.
 hipError_t launch_batch_step(uint32_t* words, int64_t count, int64_t W, int64_t H, bool bounded, int64_t samples,
                              int64_t every, uint32_t* trace, int group_waves, uint32_t rule, bool force_table,
-                             hipStream_t s);
+                             const uint32_t* rules, hipStream_t s);
 // out[2 i] = population, out[2 i + 1] = canonical hash partial sum of board i (gol_hash_finalize(partial, W, H))
 hipError_t launch_batch_observe(const uint32_t* words, int64_t count, int64_t W, int64_t H, unsigned long long* out,
                                 hipStream_t s);
@@ -278,8 +280,9 @@ hipError_t launch_batch_splitmix(uint32_t* words, int64_t count, int64_t W, int6
 
 // ---- gol_cycles.hip: the cycle census of a batch (gol_cycle_search.h), one wave per board, boards read only.
 // out[4 i ..] = transient (-1 unresolved), period, population of B_transient, generation steps run, for
-// 1 <= max_generations <= 2^20; rule and force_table as for launch_batch_step
+// 1 <= max_generations <= 2^20; rule, force_table and rules as for launch_batch_step
 hipError_t launch_batch_cycles(const uint32_t* words, int64_t count, int64_t W, int64_t H, bool bounded,
-                               int64_t max_generations, int32_t* out, uint32_t rule, bool force_table, hipStream_t s);
+                               int64_t max_generations, int32_t* out, uint32_t rule, bool force_table,
+                               const uint32_t* rules, hipStream_t s);
 
 }  // namespace gol

@@ -71,7 +71,8 @@ __device__ __forceinline__ WaveGeom wave_geom(int W, int nl, int lane) {
 
 // The rule of a generation, as a policy of wave_generation.  RuleLife is B3/S23 by life_next's LUT tree (the code every
 // pass had before rules existed); RuleTable is any life-like rule, its packed masks (gol_rule.h rule_pack: a kernel
-// argument, so uniform over the launch) evaluated by rule_next_row.
+// argument, so uniform over the launch, or a batch's per-board table entry, uniform over the wave) evaluated by
+// rule_next_row.
 struct RuleLife {};
 struct RuleTable {
     uint32_t packed;
@@ -79,6 +80,15 @@ struct RuleTable {
 // The policy of a kernel whose trailing arguments are nothing (B3/S23) or the packed rule.
 __device__ __forceinline__ RuleLife wave_rule() { return RuleLife(); }
 __device__ __forceinline__ RuleTable wave_rule(uint32_t packed) { return RuleTable{packed}; }
+// The policy of a batch kernel's wave for its board: the two above whatever the board, or, where the trailing argument
+// is a table of one packed rule per board (gol_ensemble_set_rules), that board's entry.  `board` is wave-uniform, so
+// the entry is one scalar load, and the readfirstlane says so to the compiler wherever it cannot prove it: the rule
+// stays in a scalar register and rule_next_row's tests stay scalar, as under the launch-wide rule.
+__device__ __forceinline__ RuleLife board_rule(int64_t) { return RuleLife(); }
+__device__ __forceinline__ RuleTable board_rule(int64_t, uint32_t packed) { return RuleTable{packed}; }
+__device__ __forceinline__ RuleTable board_rule(int64_t board, const uint32_t* rules) {
+    return RuleTable{(uint32_t)__builtin_amdgcn_readfirstlane((int)rules[board])};
+}
 
 // One synchronous generation of the wave's board, in place in w.  Whatever the rule gives birth on: a row outside a
 // bounded board contributes zero sums (up_mask / dn_mask) and is no cell of the board, the last word is cut to the

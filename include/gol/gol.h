@@ -306,6 +306,17 @@ int gol_batch_synchronize(gol_batch* b);
  *     was.  A new batch is B3/S23.  The rule is a property of the handle and changes only the future: cells, the generation counter,
  *     populations and hashes are untouched, and set_cells, the seeds and clear keep it.  It is the rule of
  *     gol_batch_step, gol_batch_step_timed, gol_batch_step_trace and gol_ensemble_cycles.
+ *   gol_ensemble_set_rules / gol_ensemble_rules  one rule per board: board i runs under
+ *     (birth[i], survive[i]) from now on, so one batch surveys one soup under thousands of rules -- all 2^18 fit -- in
+ *     one launch.  n == count, both arrays non-null, every mask in 0..0x1FF; anything else is GOL_ERR_INVALID before
+ *     any device work, the whole table judged first and the batch's rules exactly as they were.  The arrays are read
+ *     before the call returns; the table lives on the batch's device as count packed words, uploaded on the batch's
+ *     stream before any later step.  Like the one rule it changes only the future and set_cells, the seeds and clear
+ *     keep it, and it is the rule source of the same four calls; each wave reads its board's entry once, into a scalar
+ *     register.  gol_ensemble_set_rule afterwards puts the batch back under one rule and the kernels it ran before.
+ *     gol_ensemble_rules returns the table, or count copies of the one rule; either output may be NULL.
+ *     gol_ensemble_rule on a batch with a table returns the rule all count entries agree on, or GOL_ERR_UNSUPPORTED
+ *     with its outputs untouched where they differ.
  *   Boundaries: on a bounded board the cells outside are dead forever and are no cells of the board, also under a rule
  *     with B0; on a torus every cell has 8 neighbours (on a 3-wide or 3-high torus the other cells of the 3-line).
  *   gol_set_rule / gol_rule  the same for a single board (gol_board), masks as gol_rule_parse gives them.  A new board
@@ -324,6 +335,8 @@ int gol_rule_parse(const char* text, int* birth, int* survive);
 int gol_rule_format(int birth, int survive, char* out, int64_t len);
 int gol_ensemble_set_rule(gol_batch* b, int birth, int survive);
 int gol_ensemble_rule(gol_batch* b, int* birth, int* survive);
+int gol_ensemble_set_rules(gol_batch* b, const int* birth, const int* survive, int64_t n);
+int gol_ensemble_rules(gol_batch* b, int* birth, int* survive, int64_t n);
 int gol_set_rule(gol_board* b, int birth, int survive);
 int gol_rule(gol_board* b, int* birth, int* survive);
 /* The ensemble's cycle census: for every board, after how many generations it enters a cycle and of

@@ -127,6 +127,31 @@ class Batch {
         check(gol_rule_format(birth, survive, text, sizeof text), "gol_rule_format");
         return text;
     }
+    // one rule per board (gol_ensemble_set_rules): count texts as setRule takes them, or count mask pairs; board i runs
+    // under the i-th from now on, until another table or setRule.  rule() then throws where the boards differ
+    Batch& setRules(const std::vector<std::string>& rules) {
+        std::vector<int> birth(rules.size()), survive(rules.size());
+        for (size_t i = 0; i < rules.size(); i++)
+            check(gol_rule_parse(rules[i].c_str(), &birth[i], &survive[i]), "gol_rule_parse");
+        return setRules(birth, survive);
+    }
+    Batch& setRules(const std::vector<int>& birth, const std::vector<int>& survive) {
+        check(gol_ensemble_set_rules(b_, birth.data(), survive.data(),
+                                     birth.size() == survive.size() ? (int64_t)birth.size() : -1),
+              "gol_ensemble_set_rules");
+        return *this;
+    }
+    std::vector<std::string> rules() const {  // canonical, one per board: the table, or count times the one rule
+        std::vector<int> birth((size_t)n_), survive((size_t)n_);
+        check(gol_ensemble_rules(b_, birth.data(), survive.data(), n_), "gol_ensemble_rules");
+        std::vector<std::string> out((size_t)n_);
+        char text[22];
+        for (size_t i = 0; i < out.size(); i++) {
+            check(gol_rule_format(birth[i], survive[i], text, sizeof text), "gol_rule_format");
+            out[i] = text;
+        }
+        return out;
+    }
     Batch& step(int64_t generations = 1) {
         check(gol_batch_step(b_, generations), "gol_batch_step");
         return *this;
