@@ -24,6 +24,8 @@ HEADERS = [
     os.path.join(CSRC, "gol_debug.h"),
     os.path.join(CSRC, "gol_view.h"),
     os.path.join(CSRC, "gol_wave_body.h"),
+    os.path.join(CSRC, "gol_wave_dispatch.h"),
+    os.path.join(CSRC, "gol_wave_shape.h"),
     os.path.join(CSRC, "gol_batch_host.h"),
     os.path.join(CSRC, "gol_cycle_search.h"),
     os.path.join(CSRC, "gol_rule.h"),

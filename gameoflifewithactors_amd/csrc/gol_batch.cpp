@@ -101,7 +101,7 @@ int observe(gol_batch* b, std::vector<unsigned long long>& host) {
 
 extern "C" {
 
-int gol_batch_supported(int64_t width, int64_t height) { return gol::batch_rpl(width, height); }
+int gol_batch_supported(int64_t width, int64_t height) { return gol::wave_resident_rpl(width, height); }
 
 int gol_batch_create(int64_t width, int64_t height, int boundary, int64_t count, gol_batch** out) {
     return gol::guarded([&] {
@@ -113,8 +113,7 @@ int gol_batch_create(int64_t width, int64_t height, int boundary, int64_t count,
             return fail(GOL_ERR_INVALID, "board too large");
         if (boundary != GOL_TORUS && boundary != GOL_BOUNDED) return fail(GOL_ERR_INVALID, "bad boundary");
         if (count < 1 || count > gol::kBatchCountMax) return fail(GOL_ERR_INVALID, "count must be 1..2^22");
-        const int rpl = gol::batch_rpl(width, height);
-        if (!rpl || rpl != gol::wave_resident_rpl(width, height))
+        if (!gol::wave_resident_rpl(width, height))
             return fail(GOL_ERR_UNSUPPORTED, "a batch takes the single-wave geometry only: width 3..128 and 1..4 rows "
                                              "per lane on at most 64 lanes (gol_batch_supported)");
         int ndev = 0, cur = 0;

@@ -14,6 +14,7 @@
 #include "gol_internal.h"
 #include "gol_rule.h"
 #include "gol_wave_body.h"
+#include "gol_wave_dispatch.h"
 
 namespace gol {
 namespace {
@@ -41,6 +42,7 @@ __global__ __launch_bounds__(256) void gol_batch_step(uint32_t* __restrict__ wor
     const bool active = lane < nl;
     uint32_t* rows = words + (board * H + lane * RPL) * NW;  // this lane's RPL * NW words
     uint32_t w[RPL][NW];
+    // (gol_wave_body.h wave_load_rows, inline: through the helper 179 of this file's 196 kernels compile differently)
 #pragma unroll
     for (int i = 0; i < RPL; i++)
 #pragma unroll
@@ -56,6 +58,7 @@ __global__ __launch_bounds__(256) void gol_batch_step(uint32_t* __restrict__ wor
     for (int t = 0; t < samples; t++) {
         for (int64_t g = 0; g < every; g++) wave_generation<NW, RPL, BOUNDED>(w, geom, rule);
         if (TRACE) {
+            // (wave_population, inline for the same reason: all 96 TRACE kernels)
             // lanes past the last active one hold whatever the arithmetic left there: they count as 0
             uint32_t pop = 0;
 #pragma unroll
@@ -158,80 +161,35 @@ __global__ void gol_batch_splitmix(uint32_t* __restrict__ words, int64_t count, 
 
 unsigned blocks(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
-template <int NW, int RPL>
-hipError_t step_nr(uint32_t* words, int64_t count, int W, int H, bool bounded, int samples, int64_t every,
-                   uint32_t* trace, int group_waves, bool table, uint32_t rule, const uint32_t* rules,
-                   hipStream_t s) {
-    const dim3 grid(blocks(count, group_waves)), block(64 * group_waves);
-#define GOL_BATCH_LAUNCH(B, T)                                                                                        \
-    if (rules)                                                                                                        \
-        hipLaunchKernelGGL((gol_batch_step<NW, RPL, B, T, const uint32_t*>), grid, block, 0, s, words, count, W, H,   \
-                           samples, every, trace, rules);                                                             \
-    else if (table)                                                                                                   \
-        hipLaunchKernelGGL((gol_batch_step<NW, RPL, B, T, uint32_t>), grid, block, 0, s, words, count, W, H, samples,      \
-                           every, trace, rule);                                                                       \
-    else                                                                                                              \
-        hipLaunchKernelGGL((gol_batch_step<NW, RPL, B, T>), grid, block, 0, s, words, count, W, H, samples, every,    \
-                           trace)
-    if (bounded) {
-        if (trace) {
-            GOL_BATCH_LAUNCH(true, true);
-        } else {
-            GOL_BATCH_LAUNCH(true, false);
-        }
-    } else {
-        if (trace) {
-            GOL_BATCH_LAUNCH(false, true);
-        } else {
-            GOL_BATCH_LAUNCH(false, false);
-        }
-    }
-#undef GOL_BATCH_LAUNCH
-    return hipGetLastError();
-}
-
-template <int NW>
-hipError_t step_n(uint32_t* words, int64_t count, int W, int H, bool bounded, int samples, int64_t every,
-                  uint32_t* trace, int group_waves, int rpl, bool table, uint32_t rule, const uint32_t* rules,
-                  hipStream_t s) {
-    switch (rpl) {
-        case 1: return step_nr<NW, 1>(words, count, W, H, bounded, samples, every, trace, group_waves, table, rule,
-                                          rules, s);
-        case 2: return step_nr<NW, 2>(words, count, W, H, bounded, samples, every, trace, group_waves, table, rule,
-                                          rules, s);
-        case 3: return step_nr<NW, 3>(words, count, W, H, bounded, samples, every, trace, group_waves, table, rule,
-                                          rules, s);
-        case 4: return step_nr<NW, 4>(words, count, W, H, bounded, samples, every, trace, group_waves, table, rule,
-                                          rules, s);
-    }
-    return hipErrorInvalidValue;
-}
-
 }  // namespace
 
 hipError_t launch_batch_step(uint32_t* words, int64_t count, int64_t W, int64_t H, bool bounded, int64_t samples,
                              int64_t every, uint32_t* trace, int group_waves, uint32_t rule, bool force_table,
                              const uint32_t* rules, hipStream_t s) {
     const int rpl = wave_resident_rpl(W, H);
-    const bool table = force_table || rule != kRuleLifePacked;  // B3/S23 runs the code it always ran
-    if (!rpl || rule >= (1u << 18) || count < 1 || count > kBatchCountMax || samples < 1 || samples > INT32_MAX || every < 1 ||
-        (!trace && samples != 1) || (group_waves != 1 && group_waves != 4))
+    if (!rpl || !rule_packed_ok(rule) || count < 1 || count > kBatchCountMax || samples < 1 || samples > INT32_MAX ||
+        every < 1 || (!trace && samples != 1) || (group_waves != 1 && group_waves != 4))
         return hipErrorInvalidValue;
-    switch ((int)((W + 31) / 32)) {
-        case 1:
-            return step_n<1>(words, count, (int)W, (int)H, bounded, (int)samples, every, trace, group_waves, rpl, table,
-                             rule, rules, s);
-        case 2:
-            return step_n<2>(words, count, (int)W, (int)H, bounded, (int)samples, every, trace, group_waves, rpl, table,
-                             rule, rules, s);
-        case 3:
-            return step_n<3>(words, count, (int)W, (int)H, bounded, (int)samples, every, trace, group_waves, rpl, table,
-                             rule, rules, s);
-        case 4:
-            return step_n<4>(words, count, (int)W, (int)H, bounded, (int)samples, every, trace, group_waves, rpl, table,
-                             rule, rules, s);
-    }
-    return hipErrorInvalidValue;
+    const dim3 grid(blocks(count, group_waves)), block(64 * group_waves);
+    const int w = (int)W, h = (int)H, n = (int)samples;
+    const auto launch = [&](auto NW, auto RPL, auto B, auto T) {
+        switch (rule_family(rule, force_table, rules)) {
+            case RuleFamily::Life:
+                hipLaunchKernelGGL((gol_batch_step<NW, RPL, B, T>), grid, block, 0, s, words, count, w, h, n, every,
+                                   trace);
+                break;
+            case RuleFamily::Table:
+                hipLaunchKernelGGL((gol_batch_step<NW, RPL, B, T, uint32_t>), grid, block, 0, s, words, count, w, h, n,
+                                   every, trace, rule);
+                break;
+            case RuleFamily::PerBoard:
+                hipLaunchKernelGGL((gol_batch_step<NW, RPL, B, T, const uint32_t*>), grid, block, 0, s, words, count, w,
+                                   h, n, every, trace, rules);
+                break;
+        }
+        return hipGetLastError();
+    };
+    return wave_dispatch(launch, (int)((W + 31) / 32), rpl, bounded, trace != nullptr);
 }
 
 hipError_t launch_batch_observe(const uint32_t* words, int64_t count, int64_t W, int64_t H, unsigned long long* out,

@@ -1,25 +1,18 @@
 // gol_batch_host.h -- the host-only arithmetic of the batch handle (gol_batch.cpp): argument ranges, the .NET seeding
-// of packed boards and the per-board rule table.  No HIP here, so tests/cpp/test_batch_host.cpp and
-// tests/cpp/test_batch_rules_host.cpp compile it alone under the address and undefined-behaviour sanitizers.
+// of packed boards and the per-board rule table; a batch's geometry is the single-wave pass's (gol_wave_shape.h
+// wave_resident_rpl).  No HIP here, so tests/cpp/test_batch_host.cpp and tests/cpp/test_batch_rules_host.cpp compile
+// it alone under the address and undefined-behaviour sanitizers.
 #pragma once
 #include <stdint.h>
 
 #include "gol_rule.h"
 #include "gol_seed_rle.h"
+#include "gol_wave_shape.h"
 
 namespace gol {
 
 constexpr int64_t kBatchCountMax = (int64_t)1 << 22;  // boards per batch
 constexpr int64_t kBatchTraceMax = (int64_t)1 << 26;  // entries of one gol_batch_step_trace call
-
-// Rows per lane of the single-wave geometry: the fewest (1..4) that divide H with at most 64 lanes, for W in 3..128;
-// 0 otherwise (gol_wave.hip wave_resident_rpl states the same rule for the kernels).
-inline int batch_rpl(int64_t W, int64_t H) {
-    if (W < 3 || W > 128 || H < 3) return 0;
-    for (int r = 1; r <= 4; r++)
-        if (H % r == 0 && H / r <= 64) return r;
-    return 0;
-}
 
 // Boards [first, first + n) lie inside [0, count) and `len` is their n * cells bytes (n >= 1; no overflow for any input).
 inline bool batch_range_ok(int64_t first, int64_t n, int64_t count, int64_t len, int64_t cells) {

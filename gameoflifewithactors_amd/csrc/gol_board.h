@@ -186,7 +186,7 @@ struct gol_board {
     uint8_t* cells(int i) { return static_cast<uint8_t*>(buf[i]); }
 
     // the rule family's passes (choose_pass): any rule but B3/S23, or B3/S23 with the "rule_table" knob
-    bool rule_family() const { return opt.rule_table || rule != gol::kRuleLifePacked; }
+    bool rule_family() const { return gol::rule_family(rule, opt.rule_table) != gol::RuleFamily::Life; }
 
     gol::StreamArgs stream_args(int64_t out_begin, int64_t out_end, int k) const {
         gol::StreamArgs a{};

@@ -13,6 +13,7 @@
 #include "gol_internal.h"
 #include "gol_rule.h"
 #include "gol_wave_body.h"
+#include "gol_wave_dispatch.h"
 
 namespace gol {
 namespace {
@@ -65,27 +66,12 @@ __global__ __launch_bounds__(64) void gol_batch_cycles(const uint32_t* __restric
     const auto load = [&]() {
         Board b;
         b.wave = &cw;
-#pragma unroll
-        for (int i = 0; i < RPL; i++)
-#pragma unroll
-            for (int j = 0; j < NW; j++) b.w[i][j] = 0;
-        if (active) {  // (an inactive lane's `rows` points past its board: never dereferenced)
-#pragma unroll
-            for (int i = 0; i < RPL; i++)
-#pragma unroll
-                for (int j = 0; j < NW; j++) b.w[i][j] = rows[i * NW + j];
-        }
+        wave_load_rows(b.w, rows, active);
         return b;
     };
     uint32_t pop = 0;
-    const CycleResult r = cycle_search<Board>(load, max_generations, [&](const Board& a) {
-        uint32_t n = 0;
-#pragma unroll
-        for (int i = 0; i < RPL; i++)
-#pragma unroll
-            for (int j = 0; j < NW; j++) n += __popc(a.w[i][j]);
-        pop = wave_sum_u32(active ? n : 0u);
-    });
+    const CycleResult r = cycle_search<Board>(load, max_generations,
+                                              [&](const Board& a) { pop = wave_population(a.w, active); });
     if (lane == 0) {
         int32_t* o = out + 4 * board;
         o[0] = r.transient;
@@ -95,61 +81,34 @@ __global__ __launch_bounds__(64) void gol_batch_cycles(const uint32_t* __restric
     }
 }
 
-template <int NW, int RPL>
-hipError_t cycles_nr(const uint32_t* words, int64_t count, int W, int H, bool bounded, int G, int32_t* out, bool table,
-                     uint32_t rule, const uint32_t* rules, hipStream_t s) {
-    const dim3 grid((unsigned)count), block(64);  // count <= 2^22
-    if (rules) {
-        if (bounded)
-            hipLaunchKernelGGL((gol_batch_cycles<NW, RPL, true, const uint32_t*>), grid, block, 0, s, words, count, W,
-                               H, G, out, rules);
-        else
-            hipLaunchKernelGGL((gol_batch_cycles<NW, RPL, false, const uint32_t*>), grid, block, 0, s, words, count, W,
-                               H, G, out, rules);
-    } else if (table) {
-        if (bounded)
-            hipLaunchKernelGGL((gol_batch_cycles<NW, RPL, true, uint32_t>), grid, block, 0, s, words, count, W, H, G, out,
-                               rule);
-        else
-            hipLaunchKernelGGL((gol_batch_cycles<NW, RPL, false, uint32_t>), grid, block, 0, s, words, count, W, H, G, out,
-                               rule);
-    } else if (bounded)
-        hipLaunchKernelGGL((gol_batch_cycles<NW, RPL, true>), grid, block, 0, s, words, count, W, H, G, out);
-    else
-        hipLaunchKernelGGL((gol_batch_cycles<NW, RPL, false>), grid, block, 0, s, words, count, W, H, G, out);
-    return hipGetLastError();
-}
-
-template <int NW>
-hipError_t cycles_n(const uint32_t* words, int64_t count, int W, int H, bool bounded, int G, int32_t* out, int rpl,
-                    bool table, uint32_t rule, const uint32_t* rules, hipStream_t s) {
-    switch (rpl) {
-        case 1: return cycles_nr<NW, 1>(words, count, W, H, bounded, G, out, table, rule, rules, s);
-        case 2: return cycles_nr<NW, 2>(words, count, W, H, bounded, G, out, table, rule, rules, s);
-        case 3: return cycles_nr<NW, 3>(words, count, W, H, bounded, G, out, table, rule, rules, s);
-        case 4: return cycles_nr<NW, 4>(words, count, W, H, bounded, G, out, table, rule, rules, s);
-    }
-    return hipErrorInvalidValue;
-}
-
 }  // namespace
 
 hipError_t launch_batch_cycles(const uint32_t* words, int64_t count, int64_t W, int64_t H, bool bounded,
                                int64_t max_generations, int32_t* out, uint32_t rule, bool force_table,
                                const uint32_t* rules, hipStream_t s) {
     const int rpl = wave_resident_rpl(W, H);
-    const bool table = force_table || rule != kRuleLifePacked;  // B3/S23 runs the code it always ran
-    if (!rpl || rule >= (1u << 18) || !words || !out || count < 1 || count > kBatchCountMax || max_generations < 1 ||
-        max_generations > kCycleGenerationsMax)
+    if (!rpl || !rule_packed_ok(rule) || !words || !out || count < 1 || count > kBatchCountMax ||
+        max_generations < 1 || max_generations > kCycleGenerationsMax)
         return hipErrorInvalidValue;
-    const int G = (int)max_generations;
-    switch ((int)((W + 31) / 32)) {
-        case 1: return cycles_n<1>(words, count, (int)W, (int)H, bounded, G, out, rpl, table, rule, rules, s);
-        case 2: return cycles_n<2>(words, count, (int)W, (int)H, bounded, G, out, rpl, table, rule, rules, s);
-        case 3: return cycles_n<3>(words, count, (int)W, (int)H, bounded, G, out, rpl, table, rule, rules, s);
-        case 4: return cycles_n<4>(words, count, (int)W, (int)H, bounded, G, out, rpl, table, rule, rules, s);
-    }
-    return hipErrorInvalidValue;
+    const dim3 grid((unsigned)count), block(64);  // count <= 2^22
+    const int w = (int)W, h = (int)H, G = (int)max_generations;
+    const auto launch = [&](auto NW, auto RPL, auto B) {
+        switch (rule_family(rule, force_table, rules)) {
+            case RuleFamily::Life:
+                hipLaunchKernelGGL((gol_batch_cycles<NW, RPL, B>), grid, block, 0, s, words, count, w, h, G, out);
+                break;
+            case RuleFamily::Table:
+                hipLaunchKernelGGL((gol_batch_cycles<NW, RPL, B, uint32_t>), grid, block, 0, s, words, count, w, h, G,
+                                   out, rule);
+                break;
+            case RuleFamily::PerBoard:
+                hipLaunchKernelGGL((gol_batch_cycles<NW, RPL, B, const uint32_t*>), grid, block, 0, s, words, count, w,
+                                   h, G, out, rules);
+                break;
+        }
+        return hipGetLastError();
+    };
+    return wave_dispatch(launch, (int)((W + 31) / 32), rpl, bounded);
 }
 
 }  // namespace gol

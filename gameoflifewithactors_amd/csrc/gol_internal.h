@@ -247,11 +247,8 @@ hipError_t launch_lanes_pass(const uint32_t* src, uint32_t* dst, int64_t W, int6
                              int64_t gens, bool bounded, unsigned epoch, int* err, uint32_t* xch, int64_t xch_words,
                              hipStream_t s, int m_opt, const CoopTuning& tune);
 
-// ---- gol_wave.hip: whole board in one wavefront's registers (W <= 128, H <= 256), all generations in one launch
-int wave_resident_rpl(int64_t W, int64_t H);  // rows per lane, 0 = the board does not fit
-// ... under the rule family (any rule but B3/S23, or "rule_table"): every board up to 128 x 256, the last lane partly
-// filled where the rows do not divide into lanes
-int wave_rule_rpl(int64_t W, int64_t H);
+// ---- gol_wave.hip: whole board in one wavefront's registers (W <= 128, H <= 256), all generations in one launch; the
+// boards it takes: gol_wave_shape.h (wave_resident_rpl, and wave_rule_rpl under the rule family).
 // rule: the packed masks (gol_rule.h rule_pack); force_table: B3/S23 through the rule-table family too
 hipError_t launch_wave_resident(const void* src, void* dst, int64_t W, int64_t H, int64_t pitch, int64_t gens,
                                 bool bounded, bool bytes, uint32_t rule, bool force_table, hipStream_t s);

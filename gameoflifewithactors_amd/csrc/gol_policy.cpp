@@ -2,6 +2,7 @@
 // the measurements behind every cut-over.  Host code: it launches nothing (gol_passes.cpp runs what is chosen here).
 // gol_board.h declares what the other files use.
 #include "gol_board.h"
+#include "gol_wave_shape.h"
 
 namespace gol {
 
@@ -99,8 +100,7 @@ bool use_resident(const gol_board* b) {
 // as one single-wave launch (board option "wave_resident" = 0 disables it).
 bool use_wave_resident(const gol_board* b) {
     if (!b->opt.wave_resident) return false;
-    // the rule family's kernels also take rows that do not divide into lanes (gol_wave.hip gol_wave_rule_partial);
-    // a B3/S23 board's choice is what it was
+    // the rule family also takes rows that do not divide into lanes; a B3/S23 board's choice is what it was
     const int rpl = b->rule_family() ? gol::wave_rule_rpl(b->W, b->H) : gol::wave_resident_rpl(b->W, b->H);
     return rpl > 0 && (!b->packed || b->ilv == 1);
 }

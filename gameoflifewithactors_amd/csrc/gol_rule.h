@@ -21,6 +21,17 @@ inline bool rule_masks_ok(int birth, int survive) {
 }
 inline uint32_t rule_pack(int birth, int survive) { return (uint32_t)birth | (uint32_t)survive << 9; }
 constexpr uint32_t kRuleLifePacked = (uint32_t)kRuleLifeBirth | (uint32_t)kRuleLifeSurvive << 9;
+inline bool rule_packed_ok(uint32_t packed) { return packed < (1u << 18); }
+
+// Which kernels a launch runs.  Life: B3/S23 by life_next, the code every pass had before rules existed.  Table: any
+// life-like rule by its packed masks -- every rule but B3/S23, and B3/S23 too under force_table (the "rule_table"
+// options).  PerBoard: a batch with a table of one packed rule per board (`rules`), whatever `rule` and force_table
+// say.
+enum class RuleFamily { Life, Table, PerBoard };
+inline RuleFamily rule_family(uint32_t rule, bool force_table, const uint32_t* rules = nullptr) {
+    if (rules) return RuleFamily::PerBoard;
+    return force_table || rule != kRuleLifePacked ? RuleFamily::Table : RuleFamily::Life;
+}
 
 // The definition: the next state of a cell with n (0..8) live neighbours among its 8.
 inline int rule_next_cell(int alive, int n, int birth, int survive) {

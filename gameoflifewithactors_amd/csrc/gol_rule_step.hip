@@ -256,7 +256,7 @@ RulePlan rule_stream_plan(int64_t W, int64_t H, int ilv, int k, bool bounded, in
 hipError_t launch_rule_stream(const uint32_t* src, uint32_t* dst, int64_t W, int64_t H, int64_t pitch, int ilv, int k,
                               bool bounded, uint32_t rule, int64_t seg_opt, hipStream_t s) {
     if ((ilv != 1 && ilv != 2 && ilv != 4) || W < 32 * ilv || W % (32 * ilv) || H < 1 || pitch < W / 32 || pitch % ilv ||
-        rule >= (1u << 18) || rule_stream_largest_k(k) != k)
+        !rule_packed_ok(rule) ||rule_stream_largest_k(k) != k)
         return hipErrorInvalidValue;
     const RulePlan plan = rule_stream_plan(W, H, ilv, k, bounded, seg_opt);
     if (rule_stream_grid(plan) > 0x7fffffff) return hipErrorInvalidValue;

@@ -2,12 +2,21 @@
 // pass (gol_wave.hip), the batch pass (gol_batch.hip, one wave per board) and the cycle census (gol_cycles.hip) share,
 // and the wave-wide sum the batch's population trace and the census use.
 //
-//   lane L holds rows L*RPL .. L*RPL + RPL-1 (RPL = rows per lane, H % RPL == 0, nl = H / RPL <= 64 active lanes),
+//   lane L holds rows L*RPL .. L*RPL + RPL-1 (RPL = rows per lane, nl = ceil(H / RPL) <= 64 active lanes),
 //   each as NW = ceil(W / 32) words, bit b of word j = cell 32 j + b, bits >= W zero.
 //
 // Lanes at or beyond nl run the same instructions on whatever they hold: no active lane reads them (a lane's upper
 // neighbour is lane - 1, or nl - 1 for lane 0; its lower one lane + 1, or 0 for lane nl - 1), and they are never
 // stored.
+//
+// H % RPL == 0 everywhere but under PARTIAL (gol_wave.hip, rule family only: gol_wave_shape.h wave_rule_rpl; B3/S23
+// boards never come there, their pass choice and their kernels are wave_resident_rpl's).  PARTIAL: the rows do not
+// divide into lanes, and the last lane holds only v = H - (nl - 1) RPL of them (`last_rows` below): its slots v ..
+// RPL - 1 are no rows of the board.  They are never loaded (zero), never stored and never read: row H - 1 (slot v - 1
+// of the last lane) takes the sums below it from lane 0's first row (zero on a bounded board) instead of from slot v,
+// and lane 0 takes the sums above its first row from slot v - 1 of the last lane instead of from slot RPL - 1.
+// Everything else is the rule-table generation as it is where the rows divide, and its B0 invariants hold here the
+// same way.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -93,16 +102,31 @@ __device__ __forceinline__ RuleTable board_rule(int64_t board, const uint32_t* r
 // One synchronous generation of the wave's board, in place in w.  Whatever the rule gives birth on: a row outside a
 // bounded board contributes zero sums (up_mask / dn_mask) and is no cell of the board, the last word is cut to the
 // row's cells (lastmask) before it is stored in w, and what lanes at or beyond nl hold is never read by an active lane.
-template <int NW, int RPL, bool BOUNDED, class Rule = RuleLife>
-__device__ __forceinline__ void wave_generation(uint32_t (&w)[RPL][NW], const WaveGeom& g, Rule rule = Rule()) {
+// PARTIAL (above): `last` = this is lane nl - 1, which holds `last_rows` (1 .. RPL - 1) rows of the board.
+template <int NW, int RPL, bool BOUNDED, class Rule = RuleLife, bool PARTIAL = false>
+__device__ __forceinline__ void wave_generation(uint32_t (&w)[RPL][NW], const WaveGeom& g, Rule rule = Rule(),
+                                                bool last = false, int last_rows = RPL) {
+    static_assert(!(PARTIAL && std::is_same<Rule, RuleLife>::value), "a partly filled last lane: rule family only");
     uint32_t s[RPL][NW], c[RPL][NW];
 #pragma unroll
     for (int i = 0; i < RPL; i++) ragged_row_sum<NW, BOUNDED>(w[i], g.lb, g.lbbit, s[i], c[i]);
+    uint32_t ls[NW], lc[NW];  // PARTIAL: the sums of the lane's last row of the board (else s[RPL - 1], read in place)
+    if constexpr (PARTIAL) {
+#pragma unroll
+        for (int j = 0; j < NW; j++) ls[j] = s[RPL - 1][j], lc[j] = c[RPL - 1][j];
+#pragma unroll
+        for (int i = 0; i + 1 < RPL; i++)
+#pragma unroll
+            for (int j = 0; j < NW; j++) {
+                ls[j] = (last && last_rows - 1 == i) ? s[i][j] : ls[j];
+                lc[j] = (last && last_rows - 1 == i) ? c[i][j] : lc[j];
+            }
+    }
     uint32_t us[NW], uc[NW], ds[NW], dc[NW];
 #pragma unroll
     for (int j = 0; j < NW; j++) {
-        us[j] = bperm(g.up_addr, s[RPL - 1][j]) & g.up_mask;
-        uc[j] = bperm(g.up_addr, c[RPL - 1][j]) & g.up_mask;
+        us[j] = bperm(g.up_addr, PARTIAL ? ls[j] : s[RPL - 1][j]) & g.up_mask;
+        uc[j] = bperm(g.up_addr, PARTIAL ? lc[j] : c[RPL - 1][j]) & g.up_mask;
         ds[j] = bperm(g.dn_addr, s[0][j]) & g.dn_mask;
         dc[j] = bperm(g.dn_addr, c[0][j]) & g.dn_mask;
     }
@@ -121,8 +145,20 @@ __device__ __forceinline__ void wave_generation(uint32_t (&w)[RPL][NW], const Wa
 #pragma unroll
         for (int i = 0; i < RPL; i++) {
             uint32_t v[NW];
-            rule_next_row<NW>(i == 0 ? us : s[i - 1], i == 0 ? uc : c[i - 1], s[i], c[i], i == RPL - 1 ? ds : s[i + 1],
-                              i == RPL - 1 ? dc : c[i + 1], w[i], rule.packed, v);
+            if constexpr (PARTIAL) {  // the row below the board's last row is lane 0's first, whatever its slot
+                uint32_t sN[NW], cN[NW];
+#pragma unroll
+                for (int j = 0; j < NW; j++) {
+                    const bool below_is_lane0 = i == RPL - 1 || (last && last_rows - 1 == i);
+                    sN[j] = below_is_lane0 ? ds[j] : s[i + 1 < RPL ? i + 1 : i][j];
+                    cN[j] = below_is_lane0 ? dc[j] : c[i + 1 < RPL ? i + 1 : i][j];
+                }
+                rule_next_row<NW>(i == 0 ? us : s[i - 1], i == 0 ? uc : c[i - 1], s[i], c[i], sN, cN, w[i], rule.packed,
+                                  v);
+            } else {
+                rule_next_row<NW>(i == 0 ? us : s[i - 1], i == 0 ? uc : c[i - 1], s[i], c[i],
+                                  i == RPL - 1 ? ds : s[i + 1], i == RPL - 1 ? dc : c[i + 1], w[i], rule.packed, v);
+            }
 #pragma unroll
             for (int j = 0; j < NW; j++) w[i][j] = j == NW - 1 ? v[j] & g.lastmask : v[j];
         }
@@ -143,6 +179,34 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
     v += dpp_read<0x140>(v);
     return (uint32_t)__builtin_amdgcn_readlane((int)v, 0) + (uint32_t)__builtin_amdgcn_readlane((int)v, 16) +
            (uint32_t)__builtin_amdgcn_readlane((int)v, 32) + (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
+}
+
+// A lane's RPL x NW words from `rows` (rows back to back, as in a batch), zero in a lane that holds no rows: its `rows`
+// points past its board and is never dereferenced.
+template <int NW, int RPL>
+__device__ __forceinline__ void wave_load_rows(uint32_t (&w)[RPL][NW], const uint32_t* rows, bool active) {
+#pragma unroll
+    for (int i = 0; i < RPL; i++)
+#pragma unroll
+        for (int j = 0; j < NW; j++) w[i][j] = 0;
+    if (active) {
+#pragma unroll
+        for (int i = 0; i < RPL; i++)
+#pragma unroll
+            for (int j = 0; j < NW; j++) w[i][j] = rows[i * NW + j];
+    }
+}
+
+// The board's population, the same value in every lane.  Lanes past the last active one hold whatever the arithmetic
+// left there: they count as 0.  Every lane of the wave must be executing.
+template <int NW, int RPL>
+__device__ __forceinline__ uint32_t wave_population(const uint32_t (&w)[RPL][NW], bool active) {
+    uint32_t pop = 0;
+#pragma unroll
+    for (int i = 0; i < RPL; i++)
+#pragma unroll
+        for (int j = 0; j < NW; j++) pop += __popc(w[i][j]);
+    return wave_sum_u32(active ? pop : 0u);
 }
 
 }  // namespace gol

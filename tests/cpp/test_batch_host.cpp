@@ -18,9 +18,23 @@
 int main() {
     using namespace gol;
     // ---- geometry
-    CHECK(batch_rpl(100, 100) == 2 && batch_rpl(128, 256) == 4 && batch_rpl(3, 3) == 1 && batch_rpl(127, 192) == 3);
-    CHECK(batch_rpl(129, 64) == 0 && batch_rpl(128, 255) == 0 && batch_rpl(100, 257) == 0 && batch_rpl(2, 64) == 0);
-    CHECK(batch_rpl(INT64_MAX, INT64_MAX) == 0 && batch_rpl(INT64_MIN, 5) == 0 && batch_rpl(100, INT64_MIN) == 0);
+    CHECK(wave_resident_rpl(100, 100) == 2 && wave_resident_rpl(128, 256) == 4 && wave_resident_rpl(3, 3) == 1 &&
+          wave_resident_rpl(127, 192) == 3);
+    CHECK(wave_resident_rpl(129, 64) == 0 && wave_resident_rpl(128, 255) == 0 && wave_resident_rpl(100, 257) == 0 &&
+          wave_resident_rpl(2, 64) == 0);
+    CHECK(wave_resident_rpl(INT64_MAX, INT64_MAX) == 0 && wave_resident_rpl(INT64_MIN, 5) == 0 &&
+          wave_resident_rpl(100, INT64_MIN) == 0);
+    // ... under the rule family: the last lane partly filled where the rows do not divide into lanes
+    CHECK(wave_rule_rpl(100, 101) == 2 && wave_rule_rpl(33, 127) == 2 && wave_rule_rpl(96, 190) == 3 &&
+          wave_rule_rpl(64, 191) == 3 && wave_rule_rpl(128, 255) == 4 && wave_rule_rpl(5, 253) == 4);
+    CHECK(wave_rule_rpl(100, 257) == 0 && wave_rule_rpl(129, 64) == 0);
+    CHECK(wave_rule_rpl(INT64_MAX, INT64_MAX) == 0 && wave_rule_rpl(INT64_MIN, 5) == 0 &&
+          wave_rule_rpl(100, INT64_MIN) == 0 && wave_rule_rpl(100, INT64_MAX) == 0);
+    for (int64_t W = 3; W <= 128; W++)
+        for (int64_t H = 3; H <= 256; H++) {
+            const int r = wave_resident_rpl(W, H);
+            CHECK(r == 0 || wave_rule_rpl(W, H) == r);
+        }
     // ---- board ranges: count boards of `cells` cells
     const int64_t cells = 128 * 256, count = kBatchCountMax;
     CHECK(batch_range_ok(0, count, count, count * cells, cells));

@@ -2,9 +2,12 @@
 """Compare every kernel's instruction stream between two trees of csrc/ (the parent's and this one's): cross-compile each
 .hip file of both to gfx950 assembly, renumber the labels of each kernel in order of appearance, and compare kernel by
 kernel.  Template arguments that only a later revision has (an empty trailing parameter pack) are dropped from the name
-before matching, so a kernel that gained an empty pack still meets its parent.
+before matching, so a kernel that gained an empty pack still meets its parent.  --rename OLD=NEW (a regular expression
+and its replacement, on the demangled name; may be given several times) gives a parent kernel the name it has in this
+tree, where a kernel was renamed or gained a template argument: it is then compared and counted as renamed, not as
+missing and new.
 
-    python tools/isa_compare.py <parent csrc dir> <this csrc dir> file.hip [file.hip ...]
+    python tools/isa_compare.py [--rename OLD=NEW ...] <parent csrc dir> <this csrc dir> file.hip [file.hip ...]
 """
 import os
 import re
@@ -60,21 +63,38 @@ def kernels(text):
     return out
 
 
+def renamed(name, renames):
+    """The name a parent kernel has in this tree: every OLD=NEW applied in order (re.sub on the demangled name)."""
+    for old, new in renames:
+        name = re.sub(old, new, name)
+    return name
+
+
 def main():
-    parent, this, files = sys.argv[1], sys.argv[2], sys.argv[3:]
+    args, renames = sys.argv[1:], []
+    while "--rename" in args:
+        i = args.index("--rename")
+        renames.append(tuple(args[i + 1].split("=", 1)))
+        del args[i:i + 2]
+    parent, this, files = args[0], args[1], args[2:]
     bad = 0
     with tempfile.TemporaryDirectory() as d:
         for f in files:
             a = kernels(assembly(parent, f, os.path.join(d, "a.s")))
             b = kernels(assembly(this, f, os.path.join(d, "b.s")))
+            was = {renamed(k, renames): k for k in a}  # this tree's name -> the parent's
+            a = {renamed(k, renames): v for k, v in a.items()}
+            moved = [k for k in a if was[k] != k and k in b]
             same = [k for k in a if k in b and a[k] == b[k]]
             diff = [k for k in a if k in b and a[k] != b[k]]
             gone = [k for k in a if k not in b]
             new = [k for k in b if k not in a]
             print(f"{f}: {len(a)} kernels in the parent, {len(same)} identical, {len(diff)} differ, {len(gone)} missing, "
-                  f"{len(new)} new")
+                  f"{len(new)} new" + (f", {len(moved)} renamed" if renames else ""))
             for k in diff + gone:
-                print("   ", "DIFFERS" if k in diff else "MISSING", k)
+                print("   ", "DIFFERS" if k in diff else "MISSING", was[k])
+                if k in moved:
+                    print("        renamed to", k)
             bad += len(diff) + len(gone)
     print("all parent kernels identical" if not bad else f"{bad} parent kernels differ or are missing")
     return 1 if bad else 0
