@@ -14,7 +14,8 @@
 // A wave's window is 5 D M = 80 VGPRs at (D, M) = (4, 4): 119-122 VGPRs in all, 4 waves per SIMD.  A pipeline streams its
 // segment once, so the recomputed halo rows are one cone per pipeline (K (K - 1) level-rows), not one per wave.
 // A level takes its rows in pairs and adds the two rows both outputs of a pair hold once (gol_bitlogic.h pair_sum /
-// life_next_pair): 8 + 8 / M = 10 issue slots per word and generation here.
+// life_next_pair): 8 + 8 / M = 10 issue slots per word and generation here.  On the torus kernels a stage's first
+// level takes its block-edge words from the LDS rows it reads anyway (lds_read_trip_edges): 8 moves less per trip.
 //
 // Ring protocol (per pipeline and stage boundary, no workgroup barrier): the producer writes output row j into slot
 // j mod NR and then publishes prod = rows written; the consumer waits for prod, reads the rows, and publishes
@@ -46,6 +47,7 @@
 #include <stdint.h>
 
 #include <atomic>
+#include <cstddef>
 #include <type_traits>
 #include <vector>
 
@@ -141,7 +143,8 @@ __device__ __forceinline__ void lds_read_trip(uint32_t base, u32x4& r0, u32x4& r
         : "v"(base), "i"(kRowBytes), "i"(2 * kRowBytes), "i"(3 * kRowBytes)
         : "memory");
 }
-// A level is 144 8-byte instructions back to back (v_bitop3, v_alignbit, DPP moves; 160 before the row-pair rule), and
+// A level is 144 8-byte instructions back to back (v_bitop3, v_alignbit, DPP moves; 160 before the row-pair rule; 140
+// in a torus stage's first level, whose own block-edge words come from LDS), and
 // the pass's speed follows the address they start at, modulo 8: this is the 25 % that once seemed to follow the poll
 // loops' address (lds_wait).
 // Measured, not explained (profiles/pipe_trips/; addresses by llvm-objdump -d of the device object):
@@ -159,6 +162,39 @@ __device__ __forceinline__ void lds_read_trip(uint32_t base, u32x4& r0, u32x4& r
 #endif
 __device__ __forceinline__ void level_align() {
     asm volatile(".p2align 3\n\t.rept " GOL_PIPE_STR(GOL_PIPE_LEVEL_PAD) "\n\ts_nop 0\n\t.endr");
+}
+// The same four rows and, of each, the two words next to the lane's block: the word before it (the left lane's last,
+// `pl`) and the word after it (the right lane's first, `nf`) lie 4 bytes below and 16 bytes above the block in the
+// lane-major row, so a stage's first level takes them from here, not from the neighbour lanes' registers by DPP
+// moves -- an LDS read costs no VALU issue slot, and the pass is bound by those.  Eight ds_read_b32 behind the four
+// ds_read_b128, under the same single wait; the base of the words before is formed in pl[0]'s own register (base - 4
+// does not survive the `base ^= kHalf` of a trip's end on lane 0: the borrow crosses bit 12), one v_add per trip.
+// Lanes 1..63 read as `pl` and lanes 0..62 as `nf` exactly what the moves gave them.  Lane 0's `pl` and lane 63's
+// `nf` leave the row: the last word of the row before rows[0] (of the other half, of the array before, or of the pad
+// PipeLdsPadded puts in front of the first array) and the first word of the row after (of the array after, or of the
+// counters behind the last array): every address lies in the kernel's own allocation.  What is read there is
+// arbitrary, as the other end of the wave was that the rotate brought: both lanes are halo lanes of the torus
+// kernels (of a strip, or of a remainder sub-strip; a lane past the sub-strips stores nothing), which are never
+// stored, and K <= 32 generations move their content 32 cells, less than the lane's block of 128, so it reaches no
+// stored lane (the halo argument of the header).  The bounded kernels' outer lanes are board edges and need zeros
+// there: they keep the moves.
+__device__ __forceinline__ void lds_read_trip_edges(uint32_t base, u32x4& r0, u32x4& r1, u32x4& r2, u32x4& r3,
+                                                    uint32_t (&pl)[4], uint32_t (&nf)[4]) {
+    asm volatile(
+        "ds_read_b128 %0, %12\n\tds_read_b128 %1, %12 offset:%13\n\tds_read_b128 %2, %12 offset:%14\n\t"
+        "ds_read_b128 %3, %12 offset:%15\n\t"
+        "v_add_u32 %4, -4, %12\n\t"
+        "ds_read_b32 %8, %12 offset:%16\n\tds_read_b32 %9, %12 offset:%17\n\t"
+        "ds_read_b32 %5, %4 offset:%13\n\t"
+        "ds_read_b32 %10, %12 offset:%18\n\tds_read_b32 %11, %12 offset:%19\n\t"
+        "ds_read_b32 %6, %4 offset:%14\n\tds_read_b32 %7, %4 offset:%15\n\t"
+        "ds_read_b32 %4, %4\n\t"
+        "s_waitcnt lgkmcnt(0)"
+        : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(r3), "=&v"(pl[0]), "=&v"(pl[1]), "=&v"(pl[2]), "=&v"(pl[3]),
+          "=&v"(nf[0]), "=&v"(nf[1]), "=&v"(nf[2]), "=&v"(nf[3])
+        : "v"(base), "i"(kRowBytes), "i"(2 * kRowBytes), "i"(3 * kRowBytes), "i"(kM * 4), "i"(kRowBytes + kM * 4),
+          "i"(2 * kRowBytes + kM * 4), "i"(3 * kRowBytes + kM * 4)
+        : "memory");
 }
 template <int OFF>
 __device__ __forceinline__ void lds_write_row(uint32_t base, const u32x4& w) {
@@ -192,6 +228,17 @@ __host__ __device__ __forceinline__ int64_t pipe_cut(int64_t len, int i, int n, 
     const int64_t c = (int64_t)(total * head / sum + 0.5f) - 2 * K * i;
     return c < 0 ? 0 : (c > len ? len : c);
 }
+
+// The torus kernels' LDS (lds_read_trip_edges): the bounded kernels' three arrays behind one another, so that the word
+// after the last row is the counters' first, and a pad in front, so that the word before the first row is the kernel's
+// own too (8 KB: the row arrays, whole multiples of 8 KB, keep the alignment the variable is declared at)
+template <int S, int P>
+struct PipeLdsPadded {
+    uint32_t pad[2 * kR * kWave * kM];
+    uint32_t dstage[P][2][kR][kWave * kM];
+    uint32_t ring[P][S - 1][kNT * kR][kWave * kM];
+    int ctr[P][S][2];
+};
 
 }  // namespace
 
@@ -232,12 +279,23 @@ template <int D, int S, int P, bool WRAP, bool BND>
 __global__ __launch_bounds__(kWave * S * P) __attribute__((amdgpu_waves_per_eu(S * P / 4)))
 void gol_pipe_step(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, PipeArgs a) {
     constexpr int K = D * S, NR = kNT * kR;
-    // both arrays are whole multiples of 8 KB and the only ones of that alignment, so they lie where they lay at 16;
-    // stating it lets a trip's 4 KB run change halves by one v_xor of its base
-    __shared__ __attribute__((aligned(2 * kR * kRowBytes))) uint32_t dstage[P][2][kR][kWave * kM];  // stage 0: [par][row][lane][word]
-    __shared__ __attribute__((aligned(2 * kR * kRowBytes))) uint32_t ring[P][S - 1][NR][kWave * kM];  // [slot][lane][word]
+    // the torus kernels take a stage's first-level block-edge words from LDS (lds_read_trip_edges); the bounded ones
+    // need zeros beyond the board's edges on lanes 0 and 63, which their DPP shifts fill in
+    constexpr bool EDGES = !BND;
+    using Padded = PipeLdsPadded<S, P>;
+    __shared__ __attribute__((aligned(2 * kR * kRowBytes))) Padded lds_t;
+    static_assert(offsetof(Padded, dstage) == 2 * kR * kRowBytes && offsetof(Padded, ring) % (2 * kR * kRowBytes) == 0 &&
+                      offsetof(Padded, ctr) == offsetof(Padded, ring) + sizeof(Padded::ring),
+                  "the rows keep their 8 KB alignment behind the pad, the counters lie right behind them");
+    // the bounded kernels': both arrays are whole multiples of 8 KB and the only ones of that alignment, so they lie
+    // where they lay at 16; stating it lets a trip's 4 KB run change halves by one v_xor of its base
+    __shared__ __attribute__((aligned(2 * kR * kRowBytes))) uint32_t dstage_b[P][2][kR][kWave * kM];  // stage 0: [par][row][lane][word]
+    __shared__ __attribute__((aligned(2 * kR * kRowBytes))) uint32_t ring_b[P][S - 1][NR][kWave * kM];  // [slot][lane][word]
+    __shared__ int ctr_b[P][S][2];                                                            // [0] rows out, [1] rows in
+    auto& dstage = EDGES ? lds_t.dstage : dstage_b;  // (each kernel keeps the one it names)
+    auto& ring = EDGES ? lds_t.ring : ring_b;
+    auto& ctr = EDGES ? lds_t.ctr : ctr_b;
     static_assert(kNT == 2 && 2 * D % kR == 0, "a ring of two trips; the fill ends on a trip boundary");
-    __shared__ int ctr[P][S][2];                                                            // [0] rows out, [1] rows in
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 #if defined(GOL_PIPE_MAP) && GOL_PIPE_MAP == 1  // A/B: the stages in reverse dispatch order (the last stage oldest)
@@ -379,15 +437,24 @@ void gol_pipe_step(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst,
         const int t4 = kR * t;
         // ---- inputs of trip t: rows kR t .. kR t + kR - 1
         u32x4 x[kR];
+        // the first level's block-edge words: the left lane's last word and the right lane's first, of each row
+        [[maybe_unused]] uint32_t left0[kR];
+        uint32_t right[kR];
+        const auto read_trip = [&]() __attribute__((always_inline)) {
+            if constexpr (EDGES)
+                lds_read_trip_edges(rd, x[0], x[1], x[2], x[3], left0, right);
+            else
+                lds_read_trip(rd, x[0], x[1], x[2], x[3]);
+        };
         const auto ring_in = [&](uint32_t cb) __attribute__((always_inline)) {
             lds_publish<kIn>(cb, t4);  // trip t - 1's rows were read (and used)
             wait_ge(std::integral_constant<int, kPrevOut>{}, cb, FULL || t4 + kR < n_in ? t4 + kR : n_in);
-            lds_read_trip(rd, x[0], x[1], x[2], x[3]);
+            read_trip();
         };
         if (s == 0) {
             __builtin_amdgcn_s_waitcnt(kWaitVm0);
-            lds_read_trip(rd, x[0], x[1], x[2], x[3]);
-            __builtin_amdgcn_sched_barrier(0);  // the reads before the next trip's DMAs overwrite the other parity
+            read_trip();
+            __builtin_amdgcn_sched_barrier(0);  // the reads (edge words too) before the next trip's DMAs overwrite the other parity
             if (FULL || t + 1 < T) dma_trip((t & 1) ^ 1);
         } else if (s == S - 1) {
             ring_in(cbase);
@@ -409,9 +476,10 @@ void gol_pipe_step(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst,
         // over [yt - D, yt + kR - 2] in all; a trip reaching outside the live rows zeroes the rows it computes there
         [[maybe_unused]] const int yt = (int)(y0 - K + s * D) + t4;
         [[maybe_unused]] const bool edge_trip = BND && (yt - D < a.live_lo || yt + kR - 2 >= a.live_hi);
-        uint32_t right[kR];
+        if constexpr (!EDGES) {
 #pragma unroll
-        for (int r = 0; r < kR; r++) right[r] = from_right<BND>(v[r][0]);
+            for (int r = 0; r < kR; r++) right[r] = from_right<BND>(v[r][0]);
+        }
         __builtin_amdgcn_sched_barrier(0);
         level_align();
         __builtin_amdgcn_sched_barrier(0);
@@ -422,7 +490,7 @@ void gol_pipe_step(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst,
                 // rows Y and r are the middle rows of both outputs: their sum once (pair_sum), then row Y's output with
                 // X and row r's with r + 1 (gol_bitlogic.h: 8 LUT ops per word and generation)
                 uint32_t o0[kM], o1[kM], sN[kM], cN[kM], q0[kM], q1[kM], q2[kM];
-                row_sum_block<kM>(v[r], from_left<BND>(v[r][kM - 1]), right[r], sN, cN);
+                row_sum_block<kM>(v[r], EDGES && g == 0 ? left0[r] : from_left<BND>(v[r][kM - 1]), right[r], sN, cN);
 #pragma unroll
                 for (int j = 0; j < kM; j++) {
                     pair_sum(sY[g][j], cY[g][j], sN[j], cN[j], q0[j], q1[j], q2[j]);
@@ -430,7 +498,7 @@ void gol_pipe_step(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst,
                     sX[g][j] = sN[j];
                     cX[g][j] = cN[j];
                 }
-                row_sum_block<kM>(v[r + 1], from_left<BND>(v[r + 1][kM - 1]), right[r + 1], sN, cN);
+                row_sum_block<kM>(v[r + 1], EDGES && g == 0 ? left0[r + 1] : from_left<BND>(v[r + 1][kM - 1]), right[r + 1], sN, cN);
 #pragma unroll
                 for (int j = 0; j < kM; j++) {
                     o1[j] = life_next_pair(q0[j], q1[j], q2[j], sN[j], cN[j], v[r][j]);
