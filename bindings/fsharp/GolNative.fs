@@ -115,6 +115,19 @@ extern int gol_ensemble_rule(nativeint batch, int& birth, int& survive)
 extern int gol_ensemble_set_rules(nativeint batch, int[] birth, int[] survive, int64 n)
 [<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
 extern int gol_ensemble_rules(nativeint batch, int[] birth, int[] survive, int64 n)
+// ... Generations rules (B/S/C<n>): a batch of nstates 2..8 states per cell, its state bytes and the rule's text
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int gol_generations_create(int64 width, int64 height, int boundary, int64 count, int nstates, nativeint& out)
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int gol_generations_nstates(nativeint batch, int& nstates)
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int gol_generations_set_states(nativeint batch, int64 first, int64 n, byte[] states, int64 len)
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int gol_generations_get_states(nativeint batch, int64 first, int64 n, byte[] states, int64 len)
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl, CharSet = CharSet.Ansi)>]
+extern int gol_generations_parse(string text, int& birth, int& survive, int& nstates)
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int gol_generations_format(int birth, int survive, int nstates, byte[] out, int64 len)   // len >= 25
 // ... and of a single board (B3/S23 until set; boards on several GPUs take B3/S23 only)
 [<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
 extern int gol_set_rule(nativeint board, int birth, int survive)

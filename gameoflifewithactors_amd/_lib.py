@@ -182,6 +182,13 @@ SIGNATURES = {
     # ... one rule per board of the batch (count entries each)
     "gol_ensemble_set_rules": (ctypes.c_int, [vp, ip, ip, i64]),
     "gol_ensemble_rules": (ctypes.c_int, [vp, ip, ip, i64]),
+    # ... Generations rules (B/S/C<n>): nstates states per cell, state bytes, the three-field text
+    "gol_generations_create": (ctypes.c_int, [i64, i64, ctypes.c_int, i64, ctypes.c_int, ctypes.POINTER(vp)]),
+    "gol_generations_nstates": (ctypes.c_int, [vp, ip]),
+    "gol_generations_set_states": (ctypes.c_int, [vp, i64, i64, u8p, i64]),
+    "gol_generations_get_states": (ctypes.c_int, [vp, i64, i64, u8p, i64]),
+    "gol_generations_parse": (ctypes.c_int, [ctypes.c_char_p, ip, ip, ip]),
+    "gol_generations_format": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, i64]),
     # ... and of a single board
     "gol_set_rule": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int]),
     "gol_rule": (ctypes.c_int, [vp, ip, ip]),
@@ -379,6 +386,23 @@ def rule_format(birth: int, survive: int) -> str:
     """gol_rule_format: the canonical "B<ascending digits>/S<ascending digits>" of two masks in 0..0x1FF.  Host-only."""
     buf = ctypes.create_string_buffer(22)
     check(load().gol_rule_format(birth, survive, buf, len(buf)), "gol_rule_format")
+    return buf.value.decode()
+
+
+def generations_parse(text: str) -> tuple:
+    """gol_generations_parse: ``(birth, survive, nstates)`` of "B2/S/3", "B2/S345/C4" or "B2/S/G3" (any letter case,
+    blanks around), and of every two-field text ``rule_parse`` takes, with nstates 2; ValueError for anything else.
+    Host-only."""
+    b, s, n = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    raw = text.encode() if isinstance(text, str) else text
+    check(load().gol_generations_parse(raw, ctypes.byref(b), ctypes.byref(s), ctypes.byref(n)), "gol_generations_parse")
+    return b.value, s.value, n.value
+
+
+def generations_format(birth: int, survive: int, nstates: int) -> str:
+    """gol_generations_format: ``rule_format``'s text at nstates 2, "B.../S.../C<n>" above.  Host-only."""
+    buf = ctypes.create_string_buffer(25)
+    check(load().gol_generations_format(birth, survive, nstates, buf, len(buf)), "gol_generations_format")
     return buf.value.decode()
 
 

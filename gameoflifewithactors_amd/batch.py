@@ -29,21 +29,39 @@ def _u8p(a: np.ndarray):
     return a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
 
 
+def _third(rule) -> bytes:
+    """b"/<third field>" of a rule's text, b"" where it has two fields."""
+    raw = rule.encode() if isinstance(rule, str) else rule
+    return b"/" + raw.split(b"/", 2)[2] if raw.count(b"/") >= 2 else b""
+
+
 class BoardBatch:
     """``count`` boards of width x height on the current HIP device.
 
     The geometry is the single-wave pass's: 3 <= width <= 128 and ``batch_supported(width, height) > 0`` (1 to 4 rows
     per lane on at most 64 lanes); anything else raises NotImplementedError.  boundary: ``TORUS`` or ``BOUNDED``.
-    Cell arrays are ``(n, height, width)`` uint8, nonzero = alive.  rule: a life-like rule as ``set_rule`` takes it.
+    Cell arrays are ``(n, height, width)`` uint8, nonzero = alive.  rule: a life-like rule as ``set_rule`` takes it, or
+    a Generations rule ("B2/S/3", "B2/S345/C4") whose third field is the number of states per cell.
+    nstates (2..8, fixed for the batch's life): None takes it from the rule's text (2 without a third field); a value
+    that contradicts the text raises ValueError.  With nstates > 2 a cell is dead (0), alive (1) or dying (2 ..
+    nstates - 1): ``set_states`` / ``get_states`` carry the states, and cells, populations, traces and renders see
+    state 1 only.
     """
 
-    def __init__(self, width: int, height: int, count: int, boundary: int = TORUS, rule="B3/S23"):
+    def __init__(self, width: int, height: int, count: int, boundary: int = TORUS, rule="B3/S23", nstates=None):
         self._lib = _lib.load()
+        text_states = _lib.generations_parse(rule)[2] if isinstance(rule, (str, bytes)) else None
+        if nstates is None:
+            nstates = 2 if text_states is None else text_states
+        elif text_states is not None and text_states != nstates and b"/" in _third(rule):
+            raise ValueError(f"rule {rule!r} names {text_states} states, nstates={nstates}")
         h = ctypes.c_void_p()
-        check(self._lib.gol_batch_create(width, height, boundary, count, ctypes.byref(h)), "gol_batch_create")
+        check(self._lib.gol_generations_create(width, height, boundary, count, nstates, ctypes.byref(h)),
+              "gol_generations_create")
         self._h = h
         _lib.hold(self)
         self.width, self.height, self.count, self.boundary = width, height, count, boundary
+        self.nstates = nstates
         try:
             self.set_rule(rule)
         except Exception:
@@ -90,6 +108,28 @@ class BoardBatch:
         check(self._lib.gol_batch_get_cells(self._h, first, n, _u8p(out), out.size), "gol_batch_get_cells")
         return out
 
+    def set_states(self, states, first: int = 0) -> "BoardBatch":
+        """Replace boards [first, first + n) with an (n, height, width) array of states 0 .. nstates - 1 (0 dead, 1
+        alive, above dying).  A state at or above ``nstates`` raises ValueError and leaves the batch as it was.  Resets
+        the generation counter."""
+        a = np.asarray(states)
+        if a.size and (a.min() < 0 or a.max() > 255):
+            raise ValueError("states must lie in 0 .. nstates - 1")
+        a = np.ascontiguousarray(a, dtype=np.uint8)
+        if a.ndim == 2:
+            a = a[None]
+        if a.ndim != 3 or a.shape[1:] != (self.height, self.width):
+            raise ValueError(f"states must be (n, {self.height}, {self.width}), got {a.shape}")
+        check(self._lib.gol_generations_set_states(self._h, first, a.shape[0], _u8p(a), a.size), "gol_generations_set_states")
+        return self
+
+    def get_states(self, first: int = 0, n: int | None = None) -> np.ndarray:
+        """Boards [first, first + n) (to the end by default) as an (n, height, width) uint8 array of states."""
+        n = self.count - first if n is None else n
+        out = np.empty((max(n, 0), self.height, self.width), dtype=np.uint8)
+        check(self._lib.gol_generations_get_states(self._h, first, n, _u8p(out), out.size), "gol_generations_get_states")
+        return out
+
     def render_gray8(self, board: int, alive_value: int = 128, stride: int | None = None) -> np.ndarray:
         """Gray8 frame of one board, pixels[x + y*stride] (Board.render_gray8)."""
         stride = self.width if stride is None else stride
@@ -121,9 +161,21 @@ class BoardBatch:
         "S23/B36" or "23/36") or a ``(birth, survive)`` pair of 9-bit masks (bit n: n live neighbours).  Cells, the
         generation counter, populations and hashes are untouched, and ``set_cells``, the seeds and ``clear`` keep the
         rule.  On a bounded board the cells outside stay dead under any rule, B0 included."""
-        birth, survive = _lib.rule_parse(rule) if isinstance(rule, (str, bytes)) else rule
+        birth, survive = self._masks(rule)
         check(self._lib.gol_ensemble_set_rule(self._h, int(birth), int(survive)), "gol_ensemble_set_rule")
         return self
+
+    def _masks(self, rule) -> tuple:
+        """(birth, survive) of a rule's text or pair.  A two-field text keeps the batch's ``nstates``; a third field
+        must equal it (ValueError otherwise, as for any text the parser refuses)."""
+        if not isinstance(rule, (str, bytes)):
+            return int(rule[0]), int(rule[1])
+        if not _third(rule):
+            return _lib.rule_parse(rule)
+        birth, survive, nstates = _lib.generations_parse(rule)
+        if nstates != self.nstates:
+            raise ValueError(f"rule {rule!r} names {nstates} states, the batch has {self.nstates}")
+        return birth, survive
 
     @property
     def rule(self) -> str:
@@ -131,7 +183,7 @@ class BoardBatch:
         agree on; where they differ it raises NotImplementedError (``rules`` has the list)."""
         b, s = ctypes.c_int(), ctypes.c_int()
         check(self._lib.gol_ensemble_rule(self._h, ctypes.byref(b), ctypes.byref(s)), "gol_ensemble_rule")
-        return _lib.rule_format(b.value, s.value)
+        return _lib.generations_format(b.value, s.value, self.nstates)
 
     def set_rules(self, rules) -> "BoardBatch":
         """One rule per board: board i runs every later ``step``, ``step_timed``, ``step_trace`` and ``cycles`` under
@@ -143,8 +195,7 @@ class BoardBatch:
         if isinstance(rules, np.ndarray):
             a = rules
         else:
-            a = np.array([_lib.rule_parse(r) if isinstance(r, (str, bytes)) else (int(r[0]), int(r[1]))
-                          for r in rules], dtype=np.int64).reshape(-1, 2)
+            a = np.array([self._masks(r) for r in rules], dtype=np.int64).reshape(-1, 2)
         if a.dtype.kind not in "iu" or a.ndim != 2 or a.shape[1] != 2:
             raise ValueError(f"rules must be (n, 2) integer masks, got {a.dtype} {a.shape}")
         if a.size and (a.min() < -2**31 or a.max() >= 2**31):
@@ -161,7 +212,7 @@ class BoardBatch:
         check(self._lib.gol_ensemble_rules(self._h, birth.ctypes.data_as(_lib.ip), survive.ctypes.data_as(_lib.ip),
                                            self.count), "gol_ensemble_rules")
         pairs = list(zip(birth.tolist(), survive.tolist()))
-        text = {k: _lib.rule_format(*k) for k in set(pairs)}  # a table names few distinct rules, 2^18 at the most
+        text = {k: _lib.generations_format(*k, self.nstates) for k in set(pairs)}  # a table names few distinct rules, 2^18 at the most
         return [text[k] for k in pairs]
 
     # ---------------------------------------------------------------- stepping

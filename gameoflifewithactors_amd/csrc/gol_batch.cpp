@@ -11,6 +11,7 @@
 #include "gol_board.h"
 #include "gol_cycle_search.h"
 #include "gol_debug.h"
+#include "gol_generations.h"
 #include "gol_rule.h"
 
 using gol::DeviceBuffer;
@@ -36,9 +37,14 @@ struct gol_batch {
     std::vector<uint32_t> rules_host;
     bool rule_table = false;  // B3/S23 through the rule-table kernels too (gol_debug_batch_rule_table)
     double cycles_us = -1;  // device time of the last census launch (gol_debug_ensemble_cycles_us)
+    // Generations (gol_generations.h): fixed at creation.  nstates 2 is the life-like batch: no decay
+    // plane, and every launch is the one it was before the family existed.  Above 2, `words` holds 1 + planes arrays of
+    // count * H * nw words: the alive plane first, decay plane k at words + (k + 1) * plane_stride().
+    int nstates = 2, planes = 0;
 
     int64_t cells() const { return W * H; }
     int64_t board_words() const { return H * nw; }
+    int64_t plane_stride() const { return count * board_words(); }
     uint32_t* board(int64_t i) { return words + i * board_words(); }
     const uint32_t* table() const { return rules_host.empty() ? nullptr : rules; }  // the launchers' `rules`
 };
@@ -65,8 +71,9 @@ void free_batch(gol_batch* b) {
     delete b;
 }
 
-// boards [first, first + n) <-> host bytes, a staging buffer of at most kStagingBytes at a time
-int copy_cells(gol_batch* b, int64_t first, int64_t n, const uint8_t* in, uint8_t* out) {
+// boards [first, first + n) <-> host bytes, a staging buffer of at most kStagingBytes at a time.  states: the bytes
+// are states 0 .. nstates - 1 and every plane is written / read; otherwise 0 / 1 and the alive plane alone.
+int copy_cells(gol_batch* b, int64_t first, int64_t n, const uint8_t* in, uint8_t* out, bool states = false) {
     const int64_t per = std::max<int64_t>(1, kStagingBytes / b->cells());
     DeviceBuffer staging;
     GOL_RC(staging.alloc((size_t)(std::min(per, n) * b->cells())));
@@ -75,10 +82,18 @@ int copy_cells(gol_batch* b, int64_t first, int64_t n, const uint8_t* in, uint8_
         const size_t bytes = (size_t)(m * b->cells());
         if (in) {
             GOL_HIP(hipMemcpyAsync(staging.p, in + i * b->cells(), bytes, hipMemcpyHostToDevice, b->stream));
-            GOL_HIP(gol::launch_batch_pack(staging.as<uint8_t>(), b->board(first + i), b->W, m * b->H, b->stream));
+            if (states)
+                GOL_HIP(gol::launch_gen_pack(staging.as<uint8_t>(), b->board(first + i), b->plane_stride(), b->W,
+                                             m * b->H, b->nstates, b->stream));
+            else
+                GOL_HIP(gol::launch_batch_pack(staging.as<uint8_t>(), b->board(first + i), b->W, m * b->H, b->stream));
         } else {
-            GOL_HIP(gol::launch_batch_unpack(b->board(first + i), staging.as<uint8_t>(), b->W, m * b->H, b->W, 1,
-                                             b->stream));
+            if (states)
+                GOL_HIP(gol::launch_gen_unpack(b->board(first + i), b->plane_stride(), staging.as<uint8_t>(), b->W,
+                                               m * b->H, b->nstates, b->stream));
+            else
+                GOL_HIP(gol::launch_batch_unpack(b->board(first + i), staging.as<uint8_t>(), b->W, m * b->H, b->W, 1,
+                                                 b->stream));
             GOL_HIP(hipMemcpyAsync(out + i * b->cells(), staging.p, bytes, hipMemcpyDeviceToHost, b->stream));
         }
         GOL_HIP(hipStreamSynchronize(b->stream));  // the staging buffer is reused, the host buffer borrowed
@@ -86,27 +101,43 @@ int copy_cells(gol_batch* b, int64_t first, int64_t n, const uint8_t* in, uint8_
     return GOL_OK;
 }
 
+// boards [first, first + n) of every decay plane <- 0: what a setter of 0 / 1 cells leaves of the dying cells
+int clear_decay(gol_batch* b, int64_t first, int64_t n) {
+    for (int k = 1; k <= b->planes; k++)
+        GOL_HIP(hipMemsetAsync(b->board(first) + k * b->plane_stride(), 0, (size_t)(n * b->board_words()) * 4,
+                               b->stream));
+    return GOL_OK;
+}
+
+// one launch of the batch's step: the life-like kernels at 2 states, the Generations kernel above
+hipError_t launch_step(gol_batch* b, int64_t samples, int64_t every, uint32_t* trace) {
+    if (b->planes)
+        return gol::launch_gen_step(b->words, b->count, b->W, b->H, b->boundary == GOL_BOUNDED, samples, every, trace,
+                                    b->group_waves, b->rule, b->table(), b->nstates, b->stream);
+    return gol::launch_batch_step(b->words, b->count, b->W, b->H, b->boundary == GOL_BOUNDED, samples, every, trace,
+                                  b->group_waves, b->rule, b->rule_table, b->table(), b->stream);
+}
+
 int observe(gol_batch* b, std::vector<unsigned long long>& host) {
     DeviceBuffer acc;
     const size_t bytes = (size_t)b->count * 2 * sizeof(unsigned long long);
     GOL_RC(acc.alloc(bytes, "observables"));
-    GOL_HIP(gol::launch_batch_observe(b->words, b->count, b->W, b->H, acc.as<unsigned long long>(), b->stream));
+    if (b->planes)
+        GOL_HIP(gol::launch_gen_observe(b->words, b->count, b->W, b->H, b->nstates, acc.as<unsigned long long>(),
+                                        b->stream));
+    else
+        GOL_HIP(gol::launch_batch_observe(b->words, b->count, b->W, b->H, acc.as<unsigned long long>(), b->stream));
     host.resize((size_t)b->count * 2);
     GOL_HIP(hipMemcpyAsync(host.data(), acc.p, bytes, hipMemcpyDeviceToHost, b->stream));
     GOL_HIP(hipStreamSynchronize(b->stream));
     return GOL_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int gol_batch_supported(int64_t width, int64_t height) { return gol::wave_resident_rpl(width, height); }
-
-int gol_batch_create(int64_t width, int64_t height, int boundary, int64_t count, gol_batch** out) {
+int create_batch(int64_t width, int64_t height, int boundary, int64_t count, int nstates, gol_batch** out) {
     return gol::guarded([&] {
         if (!out) return fail(GOL_ERR_INVALID, "null out");
         *out = nullptr;
+        if (!gol::gen_states_ok(nstates)) return fail(GOL_ERR_INVALID, "nstates must be 2..8");
         if (width < 3 || height < 3)
             return fail(GOL_ERR_INVALID, "width and height must be >= 3 (smaller tori alias neighbours)");
         if (width > ((int64_t)1 << 40) || height > ((int64_t)1 << 40) || width * height > ((int64_t)1 << 42))
@@ -132,12 +163,14 @@ int gol_batch_create(int64_t width, int64_t height, int boundary, int64_t count,
         b->boundary = boundary;
         b->nw = (int)((width + 31) / 32);
         b->device = cur;
+        b->nstates = nstates;
+        b->planes = gol::gen_planes(nstates);
         hipError_t e = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking);
         if (e != hipSuccess) {
             free_batch(b);
             return fail(GOL_ERR_HIP, std::string("stream: ") + hipGetErrorString(e));
         }
-        const size_t bytes = (size_t)(count * b->board_words()) * sizeof(uint32_t);
+        const size_t bytes = (size_t)((1 + b->planes) * b->plane_stride()) * sizeof(uint32_t);
         e = hipMalloc(reinterpret_cast<void**>(&b->words), bytes);
         if (e != hipSuccess) {
             b->words = nullptr;
@@ -153,6 +186,28 @@ int gol_batch_create(int64_t width, int64_t height, int boundary, int64_t count,
         *out = b;
         return GOL_OK;
     });
+}
+
+}  // namespace
+
+extern "C" {
+
+int gol_batch_supported(int64_t width, int64_t height) { return gol::wave_resident_rpl(width, height); }
+
+int gol_batch_create(int64_t width, int64_t height, int boundary, int64_t count, gol_batch** out) {
+    return create_batch(width, height, boundary, count, 2, out);
+}
+
+int gol_generations_create(int64_t width, int64_t height, int boundary, int64_t count, int nstates,
+                                 gol_batch** out) {
+    return create_batch(width, height, boundary, count, nstates, out);
+}
+
+// reads what never changes after creation: no lock
+int gol_generations_nstates(gol_batch* b, int* nstates) {
+    if (!b || !nstates) return fail(GOL_ERR_INVALID, "null argument");
+    *nstates = b->nstates;
+    return GOL_OK;
 }
 
 int gol_batch_destroy(gol_batch* b) {
@@ -178,7 +233,28 @@ int gol_batch_set_cells(gol_batch* b, int64_t first, int64_t n, const uint8_t* c
         if (!cells || !gol::batch_range_ok(first, n, b->count, len, b->cells()))
             return fail(GOL_ERR_INVALID, "boards [first, first + n) must lie in [0, count) and len be n*width*height");
         b->generation = 0;
-        return copy_cells(b, first, n, cells, nullptr);
+        GOL_RC(copy_cells(b, first, n, cells, nullptr));
+        return clear_decay(b, first, n);
+    });
+}
+
+int gol_generations_set_states(gol_batch* b, int64_t first, int64_t n, const uint8_t* states, int64_t len) {
+    return with_batch(b, [&] {
+        if (!states || !gol::batch_range_ok(first, n, b->count, len, b->cells()))
+            return fail(GOL_ERR_INVALID, "boards [first, first + n) must lie in [0, count) and len be n*width*height");
+        for (int64_t i = 0; i < len; i++)  // before any device work: a refusal leaves the batch as it was
+            if (states[i] >= b->nstates)
+                return fail(GOL_ERR_INVALID, "a state byte is not below nstates (byte " + std::to_string(i) + ")");
+        b->generation = 0;
+        return copy_cells(b, first, n, states, nullptr, true);
+    });
+}
+
+int gol_generations_get_states(gol_batch* b, int64_t first, int64_t n, uint8_t* states, int64_t len) {
+    return with_batch(b, [&] {
+        if (!states || !gol::batch_range_ok(first, n, b->count, len, b->cells()))
+            return fail(GOL_ERR_INVALID, "boards [first, first + n) must lie in [0, count) and len be n*width*height");
+        return copy_cells(b, first, n, nullptr, states, true);
     });
 }
 
@@ -206,7 +282,7 @@ int gol_batch_seed_dotnet(gol_batch* b, const int32_t* seeds, int64_t n, int mod
             GOL_HIP(hipMemcpyAsync(b->board(i), host.data(), (size_t)(m * bw) * 4, hipMemcpyHostToDevice, b->stream));
             GOL_HIP(hipStreamSynchronize(b->stream));
         }
-        return GOL_OK;
+        return clear_decay(b, 0, b->count);
     });
 }
 
@@ -214,13 +290,13 @@ int gol_batch_seed_splitmix(gol_batch* b, uint64_t seed) {
     return with_batch(b, [&] {
         GOL_HIP(gol::launch_batch_splitmix(b->words, b->count, b->W, b->H, seed, b->stream));
         b->generation = 0;
-        return GOL_OK;
+        return clear_decay(b, 0, b->count);
     });
 }
 
 int gol_batch_clear(gol_batch* b) {
     return with_batch(b, [&] {
-        GOL_HIP(hipMemsetAsync(b->words, 0, (size_t)(b->count * b->board_words()) * 4, b->stream));
+        GOL_HIP(hipMemsetAsync(b->words, 0, (size_t)((1 + b->planes) * b->plane_stride()) * 4, b->stream));
         b->generation = 0;
         return GOL_OK;
     });
@@ -230,8 +306,7 @@ int gol_batch_step(gol_batch* b, int64_t generations) {
     return with_batch(b, [&] {
         if (generations < 0) return fail(GOL_ERR_INVALID, "generations must be >= 0");
         if (generations == 0) return GOL_OK;
-        GOL_HIP(gol::launch_batch_step(b->words, b->count, b->W, b->H, b->boundary == GOL_BOUNDED, 1, generations,
-                                       nullptr, b->group_waves, b->rule, b->rule_table, b->table(), b->stream));
+        GOL_HIP(launch_step(b, 1, generations, nullptr));
         b->generation += generations;
         return GOL_OK;
     });
@@ -244,9 +319,7 @@ int gol_batch_step_timed(gol_batch* b, int64_t generations, double* elapsed_us) 
         gol::EventPair ev;
         GOL_RC(ev.create());
         GOL_HIP(hipEventRecord(ev.e0, b->stream));
-        if (generations > 0)
-            GOL_HIP(gol::launch_batch_step(b->words, b->count, b->W, b->H, b->boundary == GOL_BOUNDED, 1, generations,
-                                           nullptr, b->group_waves, b->rule, b->rule_table, b->table(), b->stream));
+        if (generations > 0) GOL_HIP(launch_step(b, 1, generations, nullptr));
         GOL_HIP(hipEventRecord(ev.e1, b->stream));
         b->generation += generations;
         return ev.elapsed_us(elapsed_us);
@@ -263,9 +336,7 @@ int gol_batch_step_trace(gol_batch* b, int64_t generations, int64_t every, uint3
         DeviceBuffer dev;
         const size_t bytes = (size_t)len * sizeof(uint32_t);
         GOL_RC(dev.alloc(bytes, "trace"));
-        GOL_HIP(gol::launch_batch_step(b->words, b->count, b->W, b->H, b->boundary == GOL_BOUNDED, samples, every,
-                                       dev.as<uint32_t>(), b->group_waves, b->rule, b->rule_table, b->table(),
-                                       b->stream));
+        GOL_HIP(launch_step(b, samples, every, dev.as<uint32_t>()));
         b->generation += generations;
         GOL_HIP(hipMemcpyAsync(trace, dev.p, bytes, hipMemcpyDeviceToHost, b->stream));
         GOL_HIP(hipStreamSynchronize(b->stream));
@@ -295,7 +366,7 @@ int gol_batch_hashes(gol_batch* b, uint64_t* out, int64_t n) {
         if (!out || n != b->count) return fail(GOL_ERR_INVALID, "out must hold count entries");
         std::vector<unsigned long long> host;
         GOL_RC(observe(b, host));
-        for (int64_t i = 0; i < n; i++) out[i] = gol_hash_finalize(host[(size_t)(2 * i + 1)], b->W, b->H);
+        for (int64_t i = 0; i < n; i++) out[i] = gol_hash_finalize(host[(size_t)(2 * i + 1)], b->W, (b->nstates - 1) * b->H);
         return GOL_OK;
     });
 }
@@ -336,8 +407,12 @@ int gol_ensemble_cycles(gol_batch* b, int64_t max_generations, int64_t* transien
         gol::EventPair ev;
         GOL_RC(ev.create());
         GOL_HIP(hipEventRecord(ev.e0, b->stream));
-        GOL_HIP(gol::launch_batch_cycles(b->words, b->count, b->W, b->H, b->boundary == GOL_BOUNDED, max_generations,
-                                         b->cycles, b->rule, b->rule_table, b->table(), b->stream));
+        if (b->planes)
+            GOL_HIP(gol::launch_gen_cycles(b->words, b->count, b->W, b->H, b->boundary == GOL_BOUNDED, max_generations,
+                                           b->cycles, b->rule, b->table(), b->nstates, b->stream));
+        else
+            GOL_HIP(gol::launch_batch_cycles(b->words, b->count, b->W, b->H, b->boundary == GOL_BOUNDED,
+                                             max_generations, b->cycles, b->rule, b->rule_table, b->table(), b->stream));
         GOL_HIP(hipEventRecord(ev.e1, b->stream));
         GOL_HIP(hipMemcpyAsync(host.data(), b->cycles, bytes, hipMemcpyDeviceToHost, b->stream));
         GOL_HIP(hipStreamSynchronize(b->stream));
@@ -361,6 +436,19 @@ int gol_rule_parse(const char* text, int* birth, int* survive) {
 int gol_rule_format(int birth, int survive, char* out, int64_t len) {
     const char* why = "";
     return gol::rule_format(birth, survive, out, len, &why) ? GOL_OK : fail(GOL_ERR_INVALID, std::string("rule: ") + why);
+}
+
+int gol_generations_parse(const char* text, int* birth, int* survive, int* nstates) {
+    const char* why = "";
+    return gol::generations_parse(text, birth, survive, nstates, &why) ? GOL_OK
+                                                                       : fail(GOL_ERR_INVALID, std::string("rule: ") + why);
+}
+
+int gol_generations_format(int birth, int survive, int nstates, char* out, int64_t len) {
+    const char* why = "";
+    return gol::generations_format(birth, survive, nstates, out, len, &why)
+               ? GOL_OK
+               : fail(GOL_ERR_INVALID, std::string("rule: ") + why);
 }
 
 int gol_ensemble_set_rule(gol_batch* b, int birth, int survive) {

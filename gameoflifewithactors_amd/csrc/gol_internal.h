@@ -282,4 +282,24 @@ hipError_t launch_batch_cycles(const uint32_t* words, int64_t count, int64_t W, 
                                int64_t max_generations, int32_t* out, uint32_t rule, bool force_table,
                                const uint32_t* rules, hipStream_t s);
 
+// ---- gol_generations.hip: a batch under a Generations rule (gol_generations.h), nstates 3..8 for step and cycles,
+// 2..8 for the others.  `words` is the batch's alive plane (gol_batch.hip's layout); decay plane k is the same shape at
+// words + (k + 1) * plane_stride, plane_stride = count * H * NW words for the whole batch.  rule / rules as for
+// launch_batch_step (the rule-table arithmetic always); the trace and the census's population count state-1 cells.
+hipError_t launch_gen_step(uint32_t* words, int64_t count, int64_t W, int64_t H, bool bounded, int64_t samples,
+                           int64_t every, uint32_t* trace, int group_waves, uint32_t rule, const uint32_t* rules,
+                           int nstates, hipStream_t s);
+hipError_t launch_gen_cycles(const uint32_t* words, int64_t count, int64_t W, int64_t H, bool bounded,
+                             int64_t max_generations, int32_t* out, uint32_t rule, const uint32_t* rules, int nstates,
+                             hipStream_t s);
+// out[2 i] = state-1 cells, out[2 i + 1] = hash partial sum of board i's stacked board: W x (nstates - 1) H, rows
+// [(k - 1) H, k H) the indicator of state k (gol_hash_finalize(partial, W, (nstates - 1) H))
+hipError_t launch_gen_observe(const uint32_t* words, int64_t count, int64_t W, int64_t H, int nstates,
+                              unsigned long long* out, hipStream_t s);
+// `rows` rows from `words` on (a board's first row inside the batch) <-> one state byte per cell, every byte < nstates
+hipError_t launch_gen_pack(const uint8_t* states, uint32_t* words, int64_t plane_stride, int64_t W, int64_t rows,
+                           int nstates, hipStream_t s);
+hipError_t launch_gen_unpack(const uint32_t* words, int64_t plane_stride, uint8_t* out, int64_t W, int64_t rows,
+                             int nstates, hipStream_t s);
+
 }  // namespace gol

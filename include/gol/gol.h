@@ -339,6 +339,37 @@ int gol_ensemble_set_rules(gol_batch* b, const int* birth, const int* survive, i
 int gol_ensemble_rules(gol_batch* b, int* birth, int* survive, int64_t n);
 int gol_set_rule(gol_board* b, int birth, int survive);
 int gol_rule(gol_board* b, int* birth, int* survive);
+/* Generations rules on a batch (B.../S.../C<n>): a life-like rule plus n - 2 dying states.  A cell's
+ * state is s in 0 .. nstates - 1: 0 dead, 1 alive, 2 .. nstates - 1 dying; only state-1 cells count as neighbours.
+ *   s = 0 -> 1 on a birth count, else 0;  s = 1 -> 1 on a survive count, else 2 (nstates > 2) or 0 (nstates = 2);
+ *   s >= 2 -> s + 1 if s + 1 < nstates, else 0.  Boundaries as for any batch: outside a bounded board is state 0 forever.
+ * The family's calls are gol_generations_* (as the rule's and the census's are gol_ensemble_*): they take and make
+ * the same gol_batch handle, and gol_batch_* stays the plain batch's seventeen.
+ *   gol_generations_create  gol_batch_create with nstates in 2..8 (else GOL_ERR_INVALID), fixed for the handle's
+ *     life; nstates 2 is gol_batch_create itself and runs its kernels.  gol_generations_nstates returns it.
+ *   gol_generations_set_states / gol_generations_get_states  one byte per cell holding the state, boards back to
+ *     back, ranges and len as for gol_batch_set_cells.  A byte >= nstates is GOL_ERR_INVALID before any device work,
+ *     batch untouched.
+ *     set_states resets the generation counter.  Both work on a 2-state batch.
+ *   gol_generations_parse  host-only, pure.  Everything gol_rule_parse accepts, optionally followed by a third field
+ *     "/<n>", "/C<n>" or "/G<n>" (any letter case, n one digit 2..8); no third field is nstates 2.  Anything else is
+ *     GOL_ERR_INVALID with all three outputs untouched.
+ *   gol_generations_format  host-only, pure.  gol_rule_format's text for nstates 2, "B.../S.../C<n>" above, and its
+ *     NUL; len >= GOL_GENERATIONS_FORMAT_LEN (25) whatever nstates.  A refusal writes nothing.
+ * On a batch with nstates > 2: gol_ensemble_set_rule(s) / gol_ensemble_rule(s) carry birth and survive as ever (nstates
+ * is batch-wide); gol_batch_step, _step_timed and _step_trace run the transition above and the trace counts state-1
+ * cells; gol_batch_set_cells, both seeds and gol_batch_clear write states 0 and 1 only (a dying cell becomes dead);
+ * gol_batch_get_cells, gol_batch_populations and gol_batch_render_gray8 see state 1 only; gol_batch_hashes gives board
+ * i the gol_hash of a single width x (nstates - 1) * height board whose rows [(k - 1) height, k height) are the
+ * indicator of state k; gol_ensemble_cycles compares whole state boards and reports the state-1 cells of B_mu. */
+#define GOL_GENERATIONS_FORMAT_LEN 25
+int gol_generations_create(int64_t width, int64_t height, int boundary, int64_t count, int nstates,
+                                 gol_batch** out);
+int gol_generations_nstates(gol_batch* b, int* nstates);
+int gol_generations_set_states(gol_batch* b, int64_t first, int64_t n, const uint8_t* states, int64_t len);
+int gol_generations_get_states(gol_batch* b, int64_t first, int64_t n, uint8_t* states, int64_t len);
+int gol_generations_parse(const char* text, int* birth, int* survive, int* nstates);
+int gol_generations_format(int birth, int survive, int nstates, char* out, int64_t len);
 /* The ensemble's cycle census: for every board, after how many generations it enters a cycle and of
  * what period, one launch, one wavefront per board, the search in that wave's registers.
  *   Definition: B_0 = board i's current cells, B_(t+1) = the next generation of B_t under the batch's rule and boundary;
