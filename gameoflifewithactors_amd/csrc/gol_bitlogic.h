@@ -120,6 +120,98 @@ GOL_HD uint32_t life_next_pair(uint32_t q0, uint32_t q1, uint32_t q2, uint32_t s
     return lut3<0x48>(g1, g2, g3);
 }
 
+// ---- the same circuit on a block of M words, one LUT of the circuit for all M words at a time (gol_pipe.hip).
+//
+// Word by word, g1 -> g2 -> next of a word follow each other at distances of 1-3 instructions, and at 4 waves per SIMD
+// a v_bitop3 that close behind its producer issues 4-12 % slower than one 8 or more behind (DESIGN.md 4.7 "dependent
+// distance").  Stage by stage over M = 4 words, with the caller's filler between g2 and next, every LUT is 4 or more
+// behind its producer and most are 8 or more.  The stages are the LUTs of pair_sum / life_next_pair, same immediates.
+// stage_end() closes a stage: on the device an empty asm reads the stage's results (no instruction, and no register
+// written: an asm that defined them would look like a VALU write to the hazard recognizer, which then pads the level
+// with 4-byte s_nops), so the stage's LUTs stay ahead of it whatever the optimizer would rather do, and a sched_barrier
+// keeps the instruction scheduler from interleaving the stages again; on the host it is nothing.
+// tests/cpp/test_bitlogic_pair_block.cpp checks the block forms against life_next_pair and life_next.
+GOL_HD void stage_fence() {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __builtin_amdgcn_sched_barrier(0x4 | 0x10 | 0x20 | 0x40 | 0x80 | 0x100 | 0x200);  // all but VALU may cross
+#endif
+}
+GOL_HD void stage_end(const uint32_t& x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : : "v"(x));
+#else
+    (void)x;
+#endif
+    stage_fence();
+}
+template <int M>
+GOL_HD void stage_end(const uint32_t (&x)[M]) {
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+    for (int j = 0; j < M; j++) asm volatile("" : : "v"(x[j]));
+#else
+    (void)x;
+#endif
+    stage_fence();
+}
+// row_sum_block from the two funnel shifts the caller made ahead of it (w0 = align_right(r[M - 1], prev_last, 31),
+// eN = align_right(next_first, r[0], 1)): s of the words between, of word M - 1, of word 0, one by one; then c x M
+template <int M>
+GOL_HD void row_sum_block_staged(const uint32_t (&r)[M], uint32_t w0, uint32_t eN, uint32_t (&s)[M], uint32_t (&c)[M]) {
+#pragma unroll
+    for (int i = 0; i < M; i++) {
+        const int j = i == M - 1 ? 0 : i + 1;  // 1 .. M - 1, 0
+        s[j] = lut3<0x96>(j == 0 ? w0 : r[j > 0 ? j - 1 : 0], r[j], j == M - 1 ? eN : r[j < M - 1 ? j + 1 : 0]);
+        stage_end(s[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < M; j++)
+        c[j] = lut3<0xE8>(j == 0 ? w0 : r[j > 0 ? j - 1 : 0], r[j], j == M - 1 ? eN : r[j < M - 1 ? j + 1 : 0]);
+    stage_end(c);
+}
+// pair_sum: k x M, q0 x M, q1 x M, q2 x M
+template <int M>
+GOL_HD void pair_sum_block(const uint32_t (&s1)[M], const uint32_t (&c1)[M], const uint32_t (&s2)[M],
+                           const uint32_t (&c2)[M], uint32_t (&q0)[M], uint32_t (&q1)[M], uint32_t (&q2)[M]) {
+    uint32_t k[M];
+#pragma unroll
+    for (int j = 0; j < M; j++) k[j] = lut3<0x88>(s1[j], s2[j], s2[j]);
+    stage_end(k);
+#pragma unroll
+    for (int j = 0; j < M; j++) q0[j] = lut3<0x66>(s1[j], s2[j], s2[j]);
+    stage_end(q0);
+#pragma unroll
+    for (int j = 0; j < M; j++) q1[j] = lut3<0x96>(c1[j], c2[j], k[j]);
+    stage_end(q1);
+#pragma unroll
+    for (int j = 0; j < M; j++) q2[j] = lut3<0xE8>(c1[j], c2[j], k[j]);
+    stage_end(q2);
+}
+// life_next_pair in three steps: g1 x M and g3 x M; g2 x M; (the caller's filler;) next x M
+template <int M>
+GOL_HD void pair_g13_block(const uint32_t (&q0)[M], const uint32_t (&q1)[M], const uint32_t (&q2)[M],
+                           const uint32_t (&s)[M], const uint32_t (&c)[M], const uint32_t (&alive)[M], uint32_t (&g1)[M],
+                           uint32_t (&g3)[M]) {
+#pragma unroll
+    for (int j = 0; j < M; j++) g1[j] = lut3<0xE6>(q0[j], s[j], alive[j]);
+    stage_end(g1);
+#pragma unroll
+    for (int j = 0; j < M; j++) g3[j] = lut3<0x25>(q1[j], q2[j], c[j]);
+    stage_end(g3);
+}
+template <int M>
+GOL_HD void pair_g2_block(const uint32_t (&q2)[M], const uint32_t (&alive)[M], const uint32_t (&g1)[M], uint32_t (&g2)[M]) {
+#pragma unroll
+    for (int j = 0; j < M; j++) g2[j] = lut3<0x5C>(q2[j], alive[j], g1[j]);
+    stage_end(g2);
+}
+template <int M>
+GOL_HD void pair_next_block(const uint32_t (&g1)[M], const uint32_t (&g2)[M], const uint32_t (&g3)[M], uint32_t (&out)[M]) {
+#pragma unroll
+    for (int j = 0; j < M; j++) out[j] = lut3<0x48>(g1[j], g2[j], g3[j]);
+    stage_end(out);
+}
+
 // ---- any life-like rule (gol_rule.h: birth | survive << 9, uniform over a launch) on N words of one row at a time.
 //
 // t = A + 2 (B + X) + 4 Y is the 9-cell total, 0..9, as four bit planes: t0 = A, t1 = B ^ X, t2 = Y ^ (B & X),

@@ -14,7 +14,8 @@
 // A wave's window is 5 D M = 80 VGPRs at (D, M) = (4, 4): 119-122 VGPRs in all, 4 waves per SIMD.  A pipeline streams its
 // segment once, so the recomputed halo rows are one cone per pipeline (K (K - 1) level-rows), not one per wave.
 // A level takes its rows in pairs and adds the two rows both outputs of a pair hold once (gol_bitlogic.h pair_sum /
-// life_next_pair): 8 + 8 / M = 10 issue slots per word and generation here.  On the torus kernels a stage's first
+// life_next_pair): 8 + 8 / M = 10 issue slots per word and generation here, each LUT of that circuit for the block's
+// four words at a time so that none issues right behind its producer (the block forms there).  On the torus kernels a stage's first
 // level takes its block-edge words from the LDS rows it reads anyway (lds_read_trip_edges): 8 moves less per trip.
 //
 // Ring protocol (per pipeline and stage boundary, no workgroup barrier): the producer writes output row j into slot
@@ -488,22 +489,44 @@ void gol_pipe_step(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst,
 #pragma unroll
             for (int r = 0; r < kR; r += 2) {
                 // rows Y and r are the middle rows of both outputs: their sum once (pair_sum), then row Y's output with
-                // X and row r's with r + 1 (gol_bitlogic.h: 8 LUT ops per word and generation)
-                uint32_t o0[kM], o1[kM], sN[kM], cN[kM], q0[kM], q1[kM], q2[kM];
-                row_sum_block<kM>(v[r], EDGES && g == 0 ? left0[r] : from_left<BND>(v[r][kM - 1]), right[r], sN, cN);
-#pragma unroll
-                for (int j = 0; j < kM; j++) {
-                    pair_sum(sY[g][j], cY[g][j], sN[j], cN[j], q0[j], q1[j], q2[j]);
-                    o0[j] = life_next_pair(q0[j], q1[j], q2[j], sX[g][j], cX[g][j], aY[g][j]);
-                    sX[g][j] = sN[j];
-                    cX[g][j] = cN[j];
+                // X and row r's with r + 1 (gol_bitlogic.h: 8 LUT ops per word and generation).  Each LUT of the circuit
+                // for the block's four words at a time, with independent work between g2 and next (the other row's sum;
+                // a row move), so that no LUT issues right behind its producer (gol_bitlogic.h "block of M words")
+                uint32_t o0[kM], o1[kM], sA[kM], cA[kM], sB[kM], cB[kM], q0[kM], q1[kM], q2[kM], g1[kM], g2[kM], g3[kM];
+                // the left lanes' last words, then the four funnel shifts (the ones on the moved words last), ahead of
+                // both row sums
+                const uint32_t plA = EDGES && g == 0 ? left0[r] : from_left<BND>(v[r][kM - 1]);
+                const uint32_t plB = EDGES && g == 0 ? left0[r + 1] : from_left<BND>(v[r + 1][kM - 1]);
+                stage_end(plA);
+                stage_end(plB);
+                const uint32_t eA = align_right(right[r], v[r][0], 1), eB = align_right(right[r + 1], v[r + 1][0], 1);
+                stage_end(eA);
+                stage_end(eB);
+                const uint32_t wA = align_right(v[r][kM - 1], plA, 31), wB = align_right(v[r + 1][kM - 1], plB, 31);
+                stage_end(wA);
+                stage_end(wB);
+                row_sum_block_staged<kM>(v[r], wA, eA, sA, cA);
+                pair_sum_block<kM>(sY[g], cY[g], sA, cA, q0, q1, q2);
+                pair_g13_block<kM>(q0, q1, q2, sX[g], cX[g], aY[g], g1, g3);
+                pair_g2_block<kM>(q2, aY[g], g1, g2);
+                row_sum_block_staged<kM>(v[r + 1], wB, eB, sB, cB);
+                pair_next_block<kM>(g1, g2, g3, o0);
+                pair_g13_block<kM>(q0, q1, q2, sB, cB, v[r], g1, g3);
+                pair_g2_block<kM>(q2, v[r], g1, g2);
+                // (the bounded kernels' rows may still be zeroed below: their moves stay behind that)
+                if constexpr (!BND) {
+                    if (g + 1 < D) {
+                        right[r] = from_right<BND>(o0[0]);
+                        stage_end(right[r]);
+                    }
                 }
-                row_sum_block<kM>(v[r + 1], EDGES && g == 0 ? left0[r + 1] : from_left<BND>(v[r + 1][kM - 1]), right[r + 1], sN, cN);
+                pair_next_block<kM>(g1, g2, g3, o1);
 #pragma unroll
                 for (int j = 0; j < kM; j++) {
-                    o1[j] = life_next_pair(q0[j], q1[j], q2[j], sN[j], cN[j], v[r][j]);
-                    sY[g][j] = sN[j];
-                    cY[g][j] = cN[j];
+                    sX[g][j] = sA[j];
+                    cX[g][j] = cA[j];
+                    sY[g][j] = sB[j];
+                    cY[g][j] = cB[j];
                 }
                 if constexpr (BND) {
                     if (edge_trip) {  // rows outside the board stay dead (Script.fsx:6-13)
@@ -523,7 +546,7 @@ void gol_pipe_step(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst,
                     v[r + 1][j] = o1[j];
                 }
                 if (g + 1 < D) {
-                    right[r] = from_right<BND>(o0[0]);
+                    if constexpr (BND) right[r] = from_right<BND>(o0[0]);
                     right[r + 1] = from_right<BND>(o1[0]);
                     __builtin_amdgcn_sched_barrier(kAllButDs);
                 }
