@@ -72,7 +72,8 @@ void free_batch(gol_batch* b) {
 }
 
 // boards [first, first + n) <-> host bytes, a staging buffer of at most kStagingBytes at a time.  states: the bytes
-// are states 0 .. nstates - 1 and every plane is written / read; otherwise 0 / 1 and the alive plane alone.
+// are states 0 .. nstates - 1.  Otherwise: in, a byte that is not zero is state 1 and every other cell of the range dead
+// (none is left dying); out, 1 for an alive cell and 0 for every other.
 int copy_cells(gol_batch* b, int64_t first, int64_t n, const uint8_t* in, uint8_t* out, bool states = false) {
     const int64_t per = std::max<int64_t>(1, kStagingBytes / b->cells());
     DeviceBuffer staging;
@@ -82,18 +83,11 @@ int copy_cells(gol_batch* b, int64_t first, int64_t n, const uint8_t* in, uint8_
         const size_t bytes = (size_t)(m * b->cells());
         if (in) {
             GOL_HIP(hipMemcpyAsync(staging.p, in + i * b->cells(), bytes, hipMemcpyHostToDevice, b->stream));
-            if (states)
-                GOL_HIP(gol::launch_gen_pack(staging.as<uint8_t>(), b->board(first + i), b->plane_stride(), b->W,
-                                             m * b->H, b->nstates, b->stream));
-            else
-                GOL_HIP(gol::launch_batch_pack(staging.as<uint8_t>(), b->board(first + i), b->W, m * b->H, b->stream));
+            GOL_HIP(gol::launch_batch_pack(staging.as<uint8_t>(), b->board(first + i), b->plane_stride(), b->W,
+                                           m * b->H, b->nstates, states, b->stream));
         } else {
-            if (states)
-                GOL_HIP(gol::launch_gen_unpack(b->board(first + i), b->plane_stride(), staging.as<uint8_t>(), b->W,
-                                               m * b->H, b->nstates, b->stream));
-            else
-                GOL_HIP(gol::launch_batch_unpack(b->board(first + i), staging.as<uint8_t>(), b->W, m * b->H, b->W, 1,
-                                                 b->stream));
+            GOL_HIP(gol::launch_batch_unpack(b->board(first + i), b->plane_stride(), staging.as<uint8_t>(), b->W,
+                                             m * b->H, b->W, 1, b->nstates, states, b->stream));
             GOL_HIP(hipMemcpyAsync(out + i * b->cells(), staging.p, bytes, hipMemcpyDeviceToHost, b->stream));
         }
         GOL_HIP(hipStreamSynchronize(b->stream));  // the staging buffer is reused, the host buffer borrowed
@@ -101,7 +95,7 @@ int copy_cells(gol_batch* b, int64_t first, int64_t n, const uint8_t* in, uint8_
     return GOL_OK;
 }
 
-// boards [first, first + n) of every decay plane <- 0: what a setter of 0 / 1 cells leaves of the dying cells
+// boards [first, first + n) of every decay plane <- 0: what a seeder of the alive plane leaves of the dying cells
 int clear_decay(gol_batch* b, int64_t first, int64_t n) {
     for (int k = 1; k <= b->planes; k++)
         GOL_HIP(hipMemsetAsync(b->board(first) + k * b->plane_stride(), 0, (size_t)(n * b->board_words()) * 4,
@@ -109,24 +103,12 @@ int clear_decay(gol_batch* b, int64_t first, int64_t n) {
     return GOL_OK;
 }
 
-// one launch of the batch's step: the life-like kernels at 2 states, the Generations kernel above
-hipError_t launch_step(gol_batch* b, int64_t samples, int64_t every, uint32_t* trace) {
-    if (b->planes)
-        return gol::launch_gen_step(b->words, b->count, b->W, b->H, b->boundary == GOL_BOUNDED, samples, every, trace,
-                                    b->group_waves, b->rule, b->table(), b->nstates, b->stream);
-    return gol::launch_batch_step(b->words, b->count, b->W, b->H, b->boundary == GOL_BOUNDED, samples, every, trace,
-                                  b->group_waves, b->rule, b->rule_table, b->table(), b->stream);
-}
-
 int observe(gol_batch* b, std::vector<unsigned long long>& host) {
     DeviceBuffer acc;
     const size_t bytes = (size_t)b->count * 2 * sizeof(unsigned long long);
     GOL_RC(acc.alloc(bytes, "observables"));
-    if (b->planes)
-        GOL_HIP(gol::launch_gen_observe(b->words, b->count, b->W, b->H, b->nstates, acc.as<unsigned long long>(),
-                                        b->stream));
-    else
-        GOL_HIP(gol::launch_batch_observe(b->words, b->count, b->W, b->H, acc.as<unsigned long long>(), b->stream));
+    GOL_HIP(gol::launch_batch_observe(b->words, b->plane_stride(), b->count, b->W, b->H, b->nstates,
+                                      acc.as<unsigned long long>(), b->stream));
     host.resize((size_t)b->count * 2);
     GOL_HIP(hipMemcpyAsync(host.data(), acc.p, bytes, hipMemcpyDeviceToHost, b->stream));
     GOL_HIP(hipStreamSynchronize(b->stream));
@@ -233,8 +215,7 @@ int gol_batch_set_cells(gol_batch* b, int64_t first, int64_t n, const uint8_t* c
         if (!cells || !gol::batch_range_ok(first, n, b->count, len, b->cells()))
             return fail(GOL_ERR_INVALID, "boards [first, first + n) must lie in [0, count) and len be n*width*height");
         b->generation = 0;
-        GOL_RC(copy_cells(b, first, n, cells, nullptr));
-        return clear_decay(b, first, n);
+        return copy_cells(b, first, n, cells, nullptr);
     });
 }
 
@@ -306,7 +287,9 @@ int gol_batch_step(gol_batch* b, int64_t generations) {
     return with_batch(b, [&] {
         if (generations < 0) return fail(GOL_ERR_INVALID, "generations must be >= 0");
         if (generations == 0) return GOL_OK;
-        GOL_HIP(launch_step(b, 1, generations, nullptr));
+        GOL_HIP(gol::launch_batch_step(b->words, b->count, b->W, b->H, b->boundary == GOL_BOUNDED, 1, generations,
+                                      nullptr, b->group_waves, b->rule, b->rule_table, b->table(), b->nstates,
+                                      b->stream));
         b->generation += generations;
         return GOL_OK;
     });
@@ -319,7 +302,10 @@ int gol_batch_step_timed(gol_batch* b, int64_t generations, double* elapsed_us) 
         gol::EventPair ev;
         GOL_RC(ev.create());
         GOL_HIP(hipEventRecord(ev.e0, b->stream));
-        if (generations > 0) GOL_HIP(launch_step(b, 1, generations, nullptr));
+        if (generations > 0)
+            GOL_HIP(gol::launch_batch_step(b->words, b->count, b->W, b->H, b->boundary == GOL_BOUNDED, 1, generations,
+                                          nullptr, b->group_waves, b->rule, b->rule_table, b->table(), b->nstates,
+                                          b->stream));
         GOL_HIP(hipEventRecord(ev.e1, b->stream));
         b->generation += generations;
         return ev.elapsed_us(elapsed_us);
@@ -336,7 +322,9 @@ int gol_batch_step_trace(gol_batch* b, int64_t generations, int64_t every, uint3
         DeviceBuffer dev;
         const size_t bytes = (size_t)len * sizeof(uint32_t);
         GOL_RC(dev.alloc(bytes, "trace"));
-        GOL_HIP(launch_step(b, samples, every, dev.as<uint32_t>()));
+        GOL_HIP(gol::launch_batch_step(b->words, b->count, b->W, b->H, b->boundary == GOL_BOUNDED, samples, every,
+                                      dev.as<uint32_t>(), b->group_waves, b->rule, b->rule_table, b->table(), b->nstates,
+                                      b->stream));
         b->generation += generations;
         GOL_HIP(hipMemcpyAsync(trace, dev.p, bytes, hipMemcpyDeviceToHost, b->stream));
         GOL_HIP(hipStreamSynchronize(b->stream));
@@ -379,8 +367,8 @@ int gol_batch_render_gray8(gol_batch* b, int64_t board, uint8_t* pixels, int64_t
         DeviceBuffer staging;
         GOL_RC(staging.alloc(n));
         if (stride != b->W) GOL_HIP(hipMemsetAsync(staging.p, 0, n, b->stream));
-        GOL_HIP(gol::launch_batch_unpack(b->board(board), staging.as<uint8_t>(), b->W, b->H, stride, alive_value,
-                                         b->stream));
+        GOL_HIP(gol::launch_batch_unpack(b->board(board), b->plane_stride(), staging.as<uint8_t>(), b->W, b->H, stride,
+                                         alive_value, b->nstates, false, b->stream));
         GOL_HIP(hipMemcpyAsync(pixels, staging.p, n, hipMemcpyDeviceToHost, b->stream));
         GOL_HIP(hipStreamSynchronize(b->stream));
         return GOL_OK;
@@ -407,12 +395,8 @@ int gol_ensemble_cycles(gol_batch* b, int64_t max_generations, int64_t* transien
         gol::EventPair ev;
         GOL_RC(ev.create());
         GOL_HIP(hipEventRecord(ev.e0, b->stream));
-        if (b->planes)
-            GOL_HIP(gol::launch_gen_cycles(b->words, b->count, b->W, b->H, b->boundary == GOL_BOUNDED, max_generations,
-                                           b->cycles, b->rule, b->table(), b->nstates, b->stream));
-        else
-            GOL_HIP(gol::launch_batch_cycles(b->words, b->count, b->W, b->H, b->boundary == GOL_BOUNDED,
-                                             max_generations, b->cycles, b->rule, b->rule_table, b->table(), b->stream));
+        GOL_HIP(gol::launch_batch_cycles(b->words, b->count, b->W, b->H, b->boundary == GOL_BOUNDED, max_generations,
+                                         b->cycles, b->rule, b->rule_table, b->table(), b->nstates, b->stream));
         GOL_HIP(hipEventRecord(ev.e1, b->stream));
         GOL_HIP(hipMemcpyAsync(host.data(), b->cycles, bytes, hipMemcpyDeviceToHost, b->stream));
         GOL_HIP(hipStreamSynchronize(b->stream));

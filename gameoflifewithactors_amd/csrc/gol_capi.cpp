@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "gol_board.h"
+#include "gol_hash.h"
 #include "gol_rule.h"
 #include "gol_seed_rle.h"
 #include "gol_view.h"
@@ -326,15 +327,7 @@ int gol_arch_supported(const char* gcn_arch_name) {
 }
 
 uint64_t gol_hash_finalize(uint64_t h, int64_t width, int64_t height) {
-    auto fmix = [](uint64_t k) {
-        k ^= k >> 33;
-        k *= 0xff51afd7ed558ccdULL;
-        k ^= k >> 33;
-        k *= 0xc4ceb9fe1a85ec53ULL;
-        k ^= k >> 33;
-        return k;
-    };
-    return fmix(h ^ fmix((uint64_t)width * 0x100000001B3ULL + (uint64_t)height));
+    return gol::fmix64(h ^ gol::fmix64((uint64_t)width * 0x100000001B3ULL + (uint64_t)height));
 }
 
 int gol_create(int64_t width, int64_t height, int boundary, int num_gpus, int tblock_k, gol_board** out) {

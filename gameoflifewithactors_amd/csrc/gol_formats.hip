@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gol_hash.h"
 #include "gol_internal.h"
 #include "gol_layout.h"
 
@@ -299,22 +300,6 @@ __global__ void gol_bytes_render(const uint8_t* __restrict__ cells, uint8_t* __r
     if (idx >= W * H) return;
     const int64_t x = idx % W, y = idx / W;
     out[x + y * stride] = cells[idx] ? value : 0;
-}
-
-__device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
-    z += 0x9E3779B97F4A7C15ULL;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    return z ^ (z >> 31);
-}
-
-__device__ __forceinline__ uint64_t fmix64(uint64_t k) {
-    k ^= k >> 33;
-    k *= 0xff51afd7ed558ccdULL;
-    k ^= k >> 33;
-    k *= 0xc4ceb9fe1a85ec53ULL;
-    k ^= k >> 33;
-    return k;
 }
 
 // alive(x, y) = bit (x & 31) of low32(splitmix64(seed ^ (gy * ceil(W/32) + x/32)))  (DESIGN.md).

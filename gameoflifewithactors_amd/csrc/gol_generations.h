@@ -2,7 +2,7 @@
 // through before it is dead again (Brian's Brain B2/S/3, Star Wars B2/S345/4, Frogs B34/S12/3).  Its scalar definition,
 // its text forms, its bit-plane encoding and the bit-sliced decay of 32 cells per word (host + gfx950 device).  No HIP
 // here beyond gol_bitlogic.h's host/device marker: gol_batch.cpp uses it for gol_generations_parse /
-// gol_generations_format, gol_generations.hip for the kernels, and tests/cpp/test_generations.cpp compiles it alone
+// gol_generations_format, gol_batch_wave.h for the kernels, and tests/cpp/test_generations.cpp compiles it alone
 // under the address and undefined-behaviour sanitizers.
 //
 // Definition.  A cell's state is s in 0 .. C - 1, C = nstates in 2..8: 0 dead, 1 alive, 2 .. C - 1 dying.  n = the number

@@ -254,52 +254,38 @@ hipError_t launch_wave_resident(const void* src, void* dst, int64_t W, int64_t H
                                 bool bounded, bool bytes, uint32_t rule, bool force_table, hipStream_t s);
 
 // ---- gol_batch.hip: `count` boards of one single-wave geometry (wave_resident_rpl) back to back, NW = ceil(W / 32)
-// words per row, bits past W zero; one wavefront per board; count <= kBatchCountMax (gol_batch_host.h)
+// words per row, bits past W zero; one wavefront per board; count <= kBatchCountMax (gol_batch_host.h).  nstates 2..8
+// (gol_generations.h): above 2, `words` is the alive plane and decay plane k the same shape at words + (k + 1) *
+// plane_stride, plane_stride = count * H * NW words for the whole batch (gol_batch_wave.h).
 // samples x every generations of every board, in place.  trace == nullptr: samples must be 1; otherwise
-// trace[t * count + i] = population of board i after (t + 1) * every generations.  group_waves: boards (waves) per
+// trace[t * count + i] = state-1 cells of board i after (t + 1) * every generations.  group_waves: boards (waves) per
 // workgroup, 1 or 4.  rule: the packed masks (gol_rule.h rule_pack); B3/S23 runs the life_next instantiations, any
 // other rule -- or B3/S23 with force_table (gol_debug_batch_rule_table) -- the rule-table family.  rules: nullptr, or
 // `count` packed rules on the device, board i's at rules[i] (gol_ensemble_set_rules): then the per-board family runs
-// and `rule` / force_table choose nothing.
+// and `rule` / force_table choose nothing.  nstates > 2: the Generations kernel of gen_planes(nstates) planes, the
+// rule-table arithmetic always, `rule` or `rules` as above; force_table chooses nothing.
 hipError_t launch_batch_step(uint32_t* words, int64_t count, int64_t W, int64_t H, bool bounded, int64_t samples,
                              int64_t every, uint32_t* trace, int group_waves, uint32_t rule, bool force_table,
-                             const uint32_t* rules, hipStream_t s);
-// out[2 i] = population, out[2 i + 1] = canonical hash partial sum of board i (gol_hash_finalize(partial, W, H))
-hipError_t launch_batch_observe(const uint32_t* words, int64_t count, int64_t W, int64_t H, unsigned long long* out,
-                                hipStream_t s);
-// `rows` rows (of any number of boards) between one byte per cell and the packed rows; unpack writes value / 0 at
-// out[x + r * stride]
-hipError_t launch_batch_pack(const uint8_t* cells, uint32_t* words, int64_t W, int64_t rows, hipStream_t s);
-hipError_t launch_batch_unpack(const uint32_t* words, uint8_t* out, int64_t W, int64_t rows, int64_t stride,
-                               uint8_t value, hipStream_t s);
-// board i <- the cells gol_seed_splitmix(seed + i) gives a single W x H board
+                             const uint32_t* rules, int nstates, hipStream_t s);
+// out[2 i] = state-1 cells, out[2 i + 1] = canonical hash partial sum of board i's stacked board: W x (nstates - 1) H,
+// rows [(k - 1) H, k H) the indicator of state k (gol_hash_finalize(partial, W, (nstates - 1) H)); at 2 states the board
+hipError_t launch_batch_observe(const uint32_t* words, int64_t plane_stride, int64_t count, int64_t W, int64_t H,
+                                int nstates, unsigned long long* out, hipStream_t s);
+// `rows` rows from `words` on (a board's first row inside the batch; any number of boards) <-> one byte per cell.
+// states: the byte is the cell's state, every byte < nstates.  Otherwise pack takes a non-zero byte as alive and leaves
+// no dying cell; unpack writes value where the cell is alive and 0 elsewhere.  Unpack writes out[x + r * stride].
+hipError_t launch_batch_pack(const uint8_t* bytes, uint32_t* words, int64_t plane_stride, int64_t W, int64_t rows,
+                             int nstates, bool states, hipStream_t s);
+hipError_t launch_batch_unpack(const uint32_t* words, int64_t plane_stride, uint8_t* out, int64_t W, int64_t rows,
+                               int64_t stride, uint8_t value, int nstates, bool states, hipStream_t s);
+// board i's alive plane <- the cells gol_seed_splitmix(seed + i) gives a single W x H board
 hipError_t launch_batch_splitmix(uint32_t* words, int64_t count, int64_t W, int64_t H, uint64_t seed, hipStream_t s);
 
 // ---- gol_cycles.hip: the cycle census of a batch (gol_cycle_search.h), one wave per board, boards read only.
-// out[4 i ..] = transient (-1 unresolved), period, population of B_transient, generation steps run, for
-// 1 <= max_generations <= 2^20; rule, force_table and rules as for launch_batch_step
+// out[4 i ..] = transient (-1 unresolved), period, state-1 cells of B_transient, generation steps run, for
+// 1 <= max_generations <= 2^20; rule, force_table, rules and nstates as for launch_batch_step
 hipError_t launch_batch_cycles(const uint32_t* words, int64_t count, int64_t W, int64_t H, bool bounded,
                                int64_t max_generations, int32_t* out, uint32_t rule, bool force_table,
-                               const uint32_t* rules, hipStream_t s);
-
-// ---- gol_generations.hip: a batch under a Generations rule (gol_generations.h), nstates 3..8 for step and cycles,
-// 2..8 for the others.  `words` is the batch's alive plane (gol_batch.hip's layout); decay plane k is the same shape at
-// words + (k + 1) * plane_stride, plane_stride = count * H * NW words for the whole batch.  rule / rules as for
-// launch_batch_step (the rule-table arithmetic always); the trace and the census's population count state-1 cells.
-hipError_t launch_gen_step(uint32_t* words, int64_t count, int64_t W, int64_t H, bool bounded, int64_t samples,
-                           int64_t every, uint32_t* trace, int group_waves, uint32_t rule, const uint32_t* rules,
-                           int nstates, hipStream_t s);
-hipError_t launch_gen_cycles(const uint32_t* words, int64_t count, int64_t W, int64_t H, bool bounded,
-                             int64_t max_generations, int32_t* out, uint32_t rule, const uint32_t* rules, int nstates,
-                             hipStream_t s);
-// out[2 i] = state-1 cells, out[2 i + 1] = hash partial sum of board i's stacked board: W x (nstates - 1) H, rows
-// [(k - 1) H, k H) the indicator of state k (gol_hash_finalize(partial, W, (nstates - 1) H))
-hipError_t launch_gen_observe(const uint32_t* words, int64_t count, int64_t W, int64_t H, int nstates,
-                              unsigned long long* out, hipStream_t s);
-// `rows` rows from `words` on (a board's first row inside the batch) <-> one state byte per cell, every byte < nstates
-hipError_t launch_gen_pack(const uint8_t* states, uint32_t* words, int64_t plane_stride, int64_t W, int64_t rows,
-                           int nstates, hipStream_t s);
-hipError_t launch_gen_unpack(const uint32_t* words, int64_t plane_stride, uint8_t* out, int64_t W, int64_t rows,
-                             int nstates, hipStream_t s);
+                               const uint32_t* rules, int nstates, hipStream_t s);
 
 }  // namespace gol

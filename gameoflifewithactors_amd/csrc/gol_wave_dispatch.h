@@ -6,7 +6,8 @@
 //                 nw, rpl, bounded, bytes);
 //
 // calls the generic lambda with one std::integral_constant per value (each converts to its value in a constant
-// expression) and returns what it returns; hipErrorInvalidValue where nw or rpl is out of range.
+// expression) and returns what it returns; hipErrorInvalidValue where nw or rpl is out of range.  dispatch_planes does
+// the same for the decay planes of a Generations launch, around it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -21,6 +22,17 @@ hipError_t dispatch_1to4(int n, F&& f) {
         case 2: return f(std::integral_constant<int, 2>());
         case 3: return f(std::integral_constant<int, 3>());
         case 4: return f(std::integral_constant<int, 4>());
+    }
+    return hipErrorInvalidValue;
+}
+
+// (gol_generations.h gen_planes: 1..3 above 2 states)
+template <class F>
+hipError_t dispatch_planes(int planes, F&& f) {
+    switch (planes) {
+        case 1: return f(std::integral_constant<int, 1>());
+        case 2: return f(std::integral_constant<int, 2>());
+        case 3: return f(std::integral_constant<int, 3>());
     }
     return hipErrorInvalidValue;
 }

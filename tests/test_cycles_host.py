@@ -32,8 +32,10 @@ def test_the_search_header_has_no_hip():
     before, _, rest = code.partition("#if defined(__HIPCC__)")
     guarded, _, after = rest.partition("#endif")
     assert "__device__" in guarded and "__device__" not in before + after.replace("GOL_CYCLE_HD", "")
+    body = open(os.path.join(ROOT, "gameoflifewithactors_amd", "csrc", "gol_batch_wave.h")).read()
+    assert '#include "gol_cycle_search.h"' in body and "cycle_search<" in body
     kernel = open(os.path.join(ROOT, "gameoflifewithactors_amd", "csrc", "gol_cycles.hip")).read()
-    assert '#include "gol_cycle_search.h"' in kernel and "cycle_search<" in kernel
+    assert '#include "gol_batch_wave.h"' in kernel and "board_census<" in kernel
 
 
 def test_census_is_named_in_every_binding():

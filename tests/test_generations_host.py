@@ -72,7 +72,13 @@ def test_generations_are_named_in_every_binding():
         assert hasattr(lib, name) and name in _lib.SIGNATURES and name in header, name
         assert "extern int %s(" % name in fsharp, name
     assert "#define GOL_GENERATIONS_FORMAT_LEN 25" in header
-    assert any(s.endswith("gol_generations.hip") for s in build.SOURCES)
+    csrc = os.path.join(root, "gameoflifewithactors_amd", "csrc")
+    for name in ("gol_generations.h", "gol_batch_wave.h"):
+        assert os.path.join(csrc, name) in build.HEADERS, name
+    assert '#include "gol_generations.h"' in open(os.path.join(csrc, "gol_batch_wave.h")).read()
+    for name in ("gol_batch.hip", "gol_cycles.hip"):  # the step and the census kernels of the family
+        assert os.path.join(csrc, name) in build.SOURCES
+        assert '#include "gol_batch_wave.h"' in open(os.path.join(csrc, name)).read(), name
     assert lib.gol_generations_nstates(None, None) == _lib.GOL_ERR_INVALID
     assert lib.gol_generations_set_states(None, 0, 1, None, 0) == _lib.GOL_ERR_INVALID
 

@@ -1,10 +1,13 @@
 """GPU tests of Generations rules on the batch (BoardBatch(..., rule="B2/S/3") over gol_generations_create,
-gol_generations_set_states / gol_generations_get_states; csrc/gol_generations.hip): step, trace, state I/O, the
-stacked hash and the cycle census at 2 to 8 states per cell.
+gol_generations_set_states / gol_generations_get_states; csrc/gol_batch_wave.h under the kernels of csrc/gol_batch.hip
+and csrc/gol_cycles.hip): step, trace, state and cell I/O, the Gray8 frame, the stacked hash and the
+cycle census at 2 to 8 states per cell.
 
 The reference is tests/generations_reference.py (numpy, one board; pinned to tests/rule_reference.py at 2 states by
 tests/test_generations_host.py).  count is 5 or 7, so the last workgroup of 4 waves is partly filled.
 """
+import ctypes
+
 import numpy as np
 import pytest
 
@@ -155,6 +158,42 @@ def test_setters_of_cells_leave_no_dying_cell(gol, nstates):
             seed()
             assert np.array_equal(b.get_states(), b.get_cells()) and b.generation == 0
         assert b.get_states().max() == 0
+
+
+def test_cell_setters_take_any_nonzero_byte_as_alive(gol, oracle):
+    """set_cells on a Generations batch: a byte that is not zero is an alive cell, whatever its value -- a 2 or a 3 is
+    no dying state -- and the boards it does not name keep theirs."""
+    w, h, nstates = 33, 12, 4
+    start = _states(w, h, 5, nstates)
+    assert set(np.unique(start).tolist()) == set(range(nstates))
+    cells = np.random.default_rng(71).choice(np.array([0, 1, 2, 3, 255], dtype=np.uint8), (2, h, w))
+    assert all(set(np.unique(c).tolist()) == {0, 1, 2, 3, 255} for c in cells)
+    want = start.copy()
+    want[1:3] = cells != 0
+    with gol.BoardBatch(w, h, 5, TORUS, rule="B2/S345", nstates=nstates) as b:
+        got = b.set_states(start).set_cells(cells, first=1).get_states()
+        assert np.array_equal(got[1:3], (cells != 0).astype(np.uint8)) and got[1:3].max() == 1
+        assert np.array_equal(got[[0, 3, 4]], start[[0, 3, 4]])
+        assert b.hashes().tolist() == [gref.gen_hash(x, nstates, oracle) for x in want]
+
+
+def test_render_gray8_shows_the_alive_cells_alone(gol):
+    """The Gray8 frame of a Generations board: alive_value at state 1, 0 at every other state; the bytes between a
+    row's cells and the stride are 0, as tests/test_gpu_batch.py test_render_gray8 has them at 2 states."""
+    from gameoflifewithactors_amd import _lib
+
+    w, h, nstates, stride = 33, 12, 8, 40
+    start = _states(w, h, 5, nstates)
+    assert set(np.unique(start[3]).tolist()) == set(range(nstates))
+    with gol.BoardBatch(w, h, 5, TORUS, rule="B2/S345", nstates=nstates) as b:
+        b.set_states(start)
+        pixels = np.full(stride * h, 7, dtype=np.uint8)
+        ptr = pixels.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
+        _lib.check(b._lib.gol_batch_render_gray8(b._h, 3, ptr, stride, 200), "gol_batch_render_gray8")
+        rows = pixels.reshape(h, stride)
+        assert np.array_equal(rows[:, :w], np.where(start[3] == 1, 200, 0))
+        assert not rows[:, w:].any()
+        assert np.array_equal(b.get_states(), start)
 
 
 # ------------------------------------------------------------------ 5. trace

@@ -7,6 +7,9 @@ and its replacement, on the demangled name; may be given several times) gives a 
 tree, where a kernel was renamed or gained a template argument: it is then compared and counted as renamed, not as
 missing and new.
 
+A file argument PARENT.hip=THIS.hip[+THIS2.hip ...] compares the parent's kernels of PARENT.hip with the union of the
+kernels of this tree's THIS.hip, THIS2.hip, ...: for kernels that moved between files.
+
     python tools/isa_compare.py [--rename OLD=NEW ...] <parent csrc dir> <this csrc dir> file.hip [file.hip ...]
 """
 import os
@@ -80,8 +83,11 @@ def main():
     bad = 0
     with tempfile.TemporaryDirectory() as d:
         for f in files:
-            a = kernels(assembly(parent, f, os.path.join(d, "a.s")))
-            b = kernels(assembly(this, f, os.path.join(d, "b.s")))
+            left, _, right = f.partition("=")
+            a = kernels(assembly(parent, left, os.path.join(d, "a.s")))
+            b = {}
+            for g in (right or left).split("+"):
+                b.update(kernels(assembly(this, g, os.path.join(d, "b.s"))))
             was = {renamed(k, renames): k for k in a}  # this tree's name -> the parent's
             a = {renamed(k, renames): v for k, v in a.items()}
             moved = [k for k in a if was[k] != k and k in b]
