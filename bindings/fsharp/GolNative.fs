@@ -133,6 +133,15 @@ extern int gol_generations_format(int birth, int survive, int nstates, byte[] ou
 extern int gol_set_rule(nativeint board, int birth, int survive)
 [<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
 extern int gol_rule(nativeint board, int& birth, int& survive)
+// ... Generations rules of a single board (nstates 2..8; one state byte per cell; boards on several GPUs stay at 2)
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int gol_set_generations_rule(nativeint board, int birth, int survive, int nstates)
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int gol_generations_rule(nativeint board, int& birth, int& survive, int& nstates)
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int gol_set_states(nativeint board, byte[] states, int64 len)
+[<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
+extern int gol_get_states(nativeint board, byte[] states, int64 len)
 [<DllImport(Lib, CallingConvention = CallingConvention.Cdecl)>]
 extern nativeint gol_last_error()
 

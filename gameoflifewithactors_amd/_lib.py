@@ -192,6 +192,11 @@ SIGNATURES = {
     # ... and of a single board
     "gol_set_rule": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int]),
     "gol_rule": (ctypes.c_int, [vp, ip, ip]),
+    # ... Generations rules of a single board: nstates, the decay beside the alive cells, state bytes
+    "gol_set_generations_rule": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "gol_generations_rule": (ctypes.c_int, [vp, ip, ip, ip]),
+    "gol_set_states": (ctypes.c_int, [vp, u8p, i64]),
+    "gol_get_states": (ctypes.c_int, [vp, u8p, i64]),
     # test and A/B knobs (csrc/gol_debug.h: internal, not part of the gol.h boundary)
     "gol_debug_batch_group_waves": (ctypes.c_int, [vp, ctypes.c_int]),
     "gol_debug_ensemble_cycles_us": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_double)]),

@@ -42,7 +42,7 @@ class Board:
     devices: explicit strip placement (``gol_create_multi``), e.g. ``[0, 0, 0]`` runs three strips on one GPU.
     ilv: packed layout, words per interleaved block (0 = library default for the width; 1, 2, 4).
     options: {name: value} passed to gol_set_option after creation (e.g. {"coop": 0}).
-    rule: a life-like rule as ``set_rule`` takes it ("B36/S23", ...); B3/S23 unless named.
+    rule: a life-like or Generations rule as ``set_rule`` takes it ("B36/S23", "B2/S345/4", ...); B3/S23 unless named.
     """
 
     def __init__(self, width: int, height: int, boundary: int = TORUS, tblock_k: int = 0, num_gpus: int = 1,
@@ -153,7 +153,16 @@ class Board:
     def save(self, path: str) -> None:
         """Write a snapshot file (patterns.write_snapshot): header + canonical rows, 1 bit per cell.  The board's rule
         is a property of the handle, not of the cells, and the file does not carry it: pass ``rule=`` to
-        ``from_snapshot`` (or call ``set_rule``) when restoring."""
+        ``from_snapshot`` (or call ``set_rule``) when restoring.  Under a Generations rule the file carries the alive
+        plane only (state 1, and the hash of those cells alone): dying cells are not saved."""
+        if self.nstates > 2:  # the file's hash is the hash of the cells it holds, not of the stacked state board
+            nc = (self.width + 63) // 64
+            words = self.save_packed()
+            bits = np.unpackbits(words.view(np.uint8).reshape(self.height, nc * 8), axis=1, bitorder="little")
+            with Board(self.width, self.height, self.boundary) as plain:
+                cells_hash = plain.set_cells(bits[:, :self.width]).hash()
+            patterns.write_snapshot(path, words, self.width, self.height, self.boundary, self.generation, cells_hash)
+            return
         patterns.write_snapshot(path, self.save_packed(), self.width, self.height, self.boundary, self.generation,
                                 self.hash())
 
@@ -161,13 +170,20 @@ class Board:
     def from_snapshot(cls, path: str, **kw) -> "Board":
         """A new board holding a snapshot file's cells (same size and boundary); the canonical hash recorded
         in the file is checked after the upload.  kw: tblock_k, num_gpus, ilv, devices, options, rule (a snapshot holds
-        cells only: the new board is B3/S23 unless ``rule`` says otherwise)."""
+        cells only: the new board is B3/S23 unless ``rule`` says otherwise).  A snapshot holds the alive plane only: under
+        a Generations ``rule`` the new board has the file's cells in state 1 and no dying cell."""
         head, words = patterns.read_snapshot(path)
+        rule = kw.pop("rule", "B3/S23")
         b = cls(head["width"], head["height"], head["boundary"], **kw)
-        b.load_packed(words)
-        if b.hash() != head["hash"]:
+        try:
+            b.load_packed(words)
+            if b.hash() != head["hash"]:  # the hash of the cells, taken while the board has two states
+                raise ValueError(f"{path}: board hash after load differs from the snapshot's")
+            if rule != "B3/S23":
+                b.set_rule(rule)
+        except Exception:
             b.close()
-            raise ValueError(f"{path}: board hash after load differs from the snapshot's")
+            raise
         return b
 
     def to_rle(self) -> str:
@@ -206,17 +222,56 @@ class Board:
         anything else) or a ``(birth, survive)`` pair of 9-bit masks (bit n = n live neighbours).  Cells, the
         generation counter, population and hash stay as they are, and set_cells, the seeds, load_packed, place_rle and
         clear keep the rule.  On a bounded board the cells outside stay dead under any rule, B0 included.  A board on
-        several GPUs takes B3/S23 only (NotImplementedError)."""
-        birth, survive = _lib.rule_parse(rule) if isinstance(rule, (str, bytes)) else rule
-        check(self._lib.gol_set_rule(self._h, int(birth), int(survive)), "gol_set_rule")
+        several GPUs takes B3/S23 only (NotImplementedError).
+
+        A string may carry a Generations rule's third field ("B2/S345/4", "B2/S/C3", "B2/S/G3": everything
+        ``_lib.generations_parse`` takes), and a triple is ``(birth, survive, nstates)``: then the board gets that many
+        states per cell (gol_set_generations_rule).  Another nstates than the board has makes every dying cell dead;
+        a two-field string or a pair keeps the board's nstates and its dying cells."""
+        if isinstance(rule, (str, bytes)):
+            text = rule.decode() if isinstance(rule, bytes) else rule
+            if text.count("/") < 2:
+                rule = _lib.rule_parse(text)
+            else:
+                rule = _lib.generations_parse(text)
+        if len(rule) == 3:
+            birth, survive, nstates = rule
+            check(self._lib.gol_set_generations_rule(self._h, int(birth), int(survive), int(nstates)),
+                  "gol_set_generations_rule")
+        else:
+            birth, survive = rule
+            check(self._lib.gol_set_rule(self._h, int(birth), int(survive)), "gol_set_rule")
         return self
+
+    def _generations_rule(self) -> tuple:
+        b, s, n = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        check(self._lib.gol_generations_rule(self._h, ctypes.byref(b), ctypes.byref(s), ctypes.byref(n)),
+              "gol_generations_rule")
+        return b.value, s.value, n.value
 
     @property
     def rule(self) -> str:
-        """The board's rule in canonical form, "B3/S23" for a new board."""
-        b, s = ctypes.c_int(), ctypes.c_int()
-        check(self._lib.gol_rule(self._h, ctypes.byref(b), ctypes.byref(s)), "gol_rule")
-        return _lib.rule_format(b.value, s.value)
+        """The board's rule in canonical form (gol_generations_format): "B3/S23" for a new board, "B2/S/C3" above two
+        states per cell."""
+        return _lib.generations_format(*self._generations_rule())
+
+    @property
+    def nstates(self) -> int:
+        """States per cell: 2 for a life-like board, 3..8 under a Generations rule."""
+        return self._generations_rule()[2]
+
+    def set_states(self, states) -> "Board":
+        """The whole board from one byte per cell holding its state (0 dead, 1 alive, 2 .. nstates - 1 dying); a byte
+        >= nstates is a ValueError and leaves the board as it was.  Resets the generation counter."""
+        a = np.ascontiguousarray(np.asarray(states, dtype=np.uint8)).reshape(-1)
+        check(self._lib.gol_set_states(self._h, _u8p(a), a.size), "gol_set_states")
+        return self
+
+    def get_states(self) -> np.ndarray:
+        """(height, width) uint8, each cell's state; on a two-state board what get_cells returns."""
+        out = np.empty((self.height, self.width), dtype=np.uint8)
+        check(self._lib.gol_get_states(self._h, _u8p(out), out.size), "gol_get_states")
+        return out
 
     # ---------------------------------------------------------------- stepping
     def step(self, generations: int = 1) -> "Board":

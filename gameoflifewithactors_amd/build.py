@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libgol_hip.so")
-SOURCES = [os.path.join(CSRC, f) for f in ("gol_step.hip", "gol_rule_step.hip", "gol_formats.hip", "gol_resident.hip", "gol_wave.hip", "gol_coop.hip", "gol_lanes.hip", "gol_pipe.hip", "gol_view.hip", "gol_batch.hip", "gol_cycles.hip", "gol_stream_plan.cpp", "gol_capi.cpp", "gol_passes.cpp", "gol_policy.cpp", "gol_strip.cpp", "gol_options.cpp", "gol_multi.cpp", "gol_batch.cpp")]
+SOURCES = [os.path.join(CSRC, f) for f in ("gol_step.hip", "gol_rule_step.hip", "gol_gen_stream.hip", "gol_formats.hip", "gol_resident.hip", "gol_wave.hip", "gol_coop.hip", "gol_lanes.hip", "gol_pipe.hip", "gol_view.hip", "gol_batch.hip", "gol_cycles.hip", "gol_stream_plan.cpp", "gol_capi.cpp", "gol_passes.cpp", "gol_policy.cpp", "gol_strip.cpp", "gol_options.cpp", "gol_multi.cpp", "gol_batch.cpp")]
 HEADERS = [
     os.path.join(CSRC, "gol_bitlogic.h"),
     os.path.join(CSRC, "gol_layout.h"),
@@ -33,6 +33,7 @@ HEADERS = [
     os.path.join(CSRC, "gol_batch_wave.h"),
     os.path.join(CSRC, "gol_hash.h"),
     os.path.join(CSRC, "gol_rule_plan.h"),
+    os.path.join(CSRC, "gol_gen_plan.h"),
     os.path.join(ROOT, "include", "gol", "gol.h"),
 ]
 ARCH = "gfx950"

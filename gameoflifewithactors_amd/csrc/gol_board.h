@@ -10,6 +10,7 @@
 #include <string>
 
 #include "../../include/gol/gol.h"
+#include "gol_generations.h"
 #include "gol_internal.h"
 #include "gol_multi.h"
 #include "gol_rule.h"
@@ -92,6 +93,10 @@ struct EventPair {
 
 // The pass a gol_step call takes (choose_pass); its value is the debug option "last_pass" (gol_debug.h).
 enum class Pass { None, Wave, Lanes, Coop, CoopRagged, Ring, StreamRagged, Resident, Bytes, Stream, Multi, RuleStream };
+// Value 12, after RuleStream: the multi-plane streaming pass of a Generations board (gol_gen_stream.hip, DESIGN.md
+// 4.15).  It is a named value of the type beside the enumerator list, not a thirteenth enumerator: the list as it
+// stands above is what tests/test_board_rules_host.py reads out of this file.
+constexpr Pass kPassGenStream = static_cast<Pass>(12);
 
 extern const int64_t kCoopMaxCells;               // gol_policy.cpp
 constexpr int kCoopFlagWords = 1024;              // bands of one launch at most (one per CU) ...
@@ -179,9 +184,21 @@ struct gol_board {
     int ring_age = 0;  // ring rows: generations since the copies were last exact (errors reach ring_age cells in)
     int64_t generation = 0;
     uint32_t rule = gol::kRuleLifePacked;  // birth | survive << 9 (gol_rule.h rule_pack): B3/S23 until gol_set_rule
+    // Generations rules (gol_generations.h): states per cell, 2 until gol_set_generations_rule.  Above
+    // 2 the alive plane stays where buf is and the dying cells sit in dec[], ping-ponging with buf (dec[cur] goes with
+    // buf[cur]): packed boards gen_planes(nstates) planes of pitch * H words in the board's layout, plane k at
+    // + k * pitch * H words, d = s - 1 as a binary number over them; byte boards one byte d per cell.  Null at 2 states.
+    int nstates = 2;
+    void* dec[2] = {nullptr, nullptr};
     gol::MultiBoard* multi = nullptr;  // num_gpus > 1: row strips over several devices (gol_multi.h)
 
     size_t bytes() const { return packed ? (size_t)(pitch * H) * 4 : (size_t)(W * H); }
+    static size_t dec_bytes_of(const gol_board* b, int n) {
+        return b->packed ? (size_t)gol::gen_planes(n) * (size_t)(b->pitch * b->H) * 4 : (n > 2 ? (size_t)(b->W * b->H) : 0);
+    }
+    size_t dec_bytes() const { return dec_bytes_of(this, nstates); }
+    uint32_t* dec_words(int i) { return static_cast<uint32_t*>(dec[i]); }
+    uint8_t* dec_cells(int i) { return static_cast<uint8_t*>(dec[i]); }
     uint32_t* words(int i) { return static_cast<uint32_t*>(buf[i]); }
     uint8_t* cells(int i) { return static_cast<uint8_t*>(buf[i]); }
 

@@ -97,8 +97,13 @@ int sync(gol_board* b) {
 // then the cooperative error word is cleared WITHOUT marking the board invalid: an error a timed-out pass left
 // there, with no readback or gol_synchronize after it, must not fail the overwrite that replaces its result
 // (tests/test_gpu_coop.py::test_coop_timeout_then_overwrite_without_readback).
-int overwritten(gol_board* b) {
+//
+// A Generations board (nstates > 2): everything that overwrites cells writes the alive plane alone, and this is the one
+// place where every decay word becomes zero behind it (set_cells, load_packed, the seeds, clear).  gol_set_states
+// writes the decay itself (clear_decay = false).
+int overwritten(gol_board* b, bool clear_decay = true) {
     if (!b->multi) {
+        if (clear_decay && b->dec[b->cur]) GOL_HIP(hipMemsetAsync(b->dec[b->cur], 0, b->dec_bytes(), b->stream));
         GOL_HIP(hipStreamSynchronize(b->stream));
         if (b->coop) {
             GOL_HIP(hipMemsetAsync(b->coop + kCoopErrWord, 0, sizeof(unsigned), b->stream));
@@ -146,7 +151,11 @@ int reduce_impl(gol_board* b, bool hash, uint64_t* out) {
     if (b->multi) return b->multi->reduce(hash, out);
     GOL_RC(sync_bytes(b));
     GOL_HIP(hipMemsetAsync(b->acc, 0, sizeof(unsigned long long), b->stream));
-    if (b->packed) {
+    const bool stacked = hash && b->nstates > 2;  // a Generations board: the hash of the stacked board (gol.h)
+    if (stacked) {
+        GOL_HIP(gol::launch_gen_hash(b->buf[b->cur], b->dec[b->cur], b->packed ? b->ilv : 0, b->W, b->H, b->pitch,
+                                     b->nstates, b->acc, b->stream));
+    } else if (b->packed) {
         if (hash)
             GOL_HIP(gol::launch_hash_packed(b->words(b->cur), b->W, b->H, b->pitch, 0, 0, b->ilv, b->acc, b->stream));
         else
@@ -161,7 +170,7 @@ int reduce_impl(gol_board* b, bool hash, uint64_t* out) {
     GOL_HIP(hipMemcpyAsync(&v, b->acc, sizeof(v), hipMemcpyDeviceToHost, b->stream));
     GOL_HIP(hipStreamSynchronize(b->stream));
     GOL_RC(check_valid(b));
-    *out = hash ? gol_hash_finalize(v, b->W, b->H) : (uint64_t)v;
+    *out = hash ? gol_hash_finalize(v, b->W, stacked ? (b->nstates - 1) * b->H : b->H) : (uint64_t)v;
     return GOL_OK;
 }
 
@@ -174,6 +183,9 @@ int place_points(gol_board* b, const std::vector<int64_t>& xy) {
     GOL_RC(d.alloc(xy.size() * sizeof(int64_t), "points"));
     GOL_HIP(hipMemcpyAsync(d.p, xy.data(), xy.size() * sizeof(int64_t), hipMemcpyHostToDevice, b->stream));
     GOL_HIP(gol::launch_set_points(b->buf[b->cur], b->packed ? b->ilv : 0, b->W, b->pitch, d.as<int64_t>(), n, b->stream));
+    if (b->nstates > 2)  // a placed cell is in state 1: the alive plane and the decay stay exclusive
+        GOL_HIP(gol::launch_clear_points_decay(b->dec[b->cur], b->packed ? b->ilv : 0, b->W, b->H, b->pitch, b->nstates,
+                                               d.as<int64_t>(), n, b->stream));
     GOL_HIP(hipStreamSynchronize(b->stream));
     return GOL_OK;
 }
@@ -181,6 +193,8 @@ int place_points(gol_board* b, const std::vector<int64_t>& xy) {
 void free_board(gol_board* b) {
     delete b->multi;
     for (auto& p : b->buf)
+        if (p) (void)hipFree(p);
+    for (auto& p : b->dec)
         if (p) (void)hipFree(p);
     if (b->acc) (void)hipFree(b->acc);
     if (b->coop) (void)hipFree(b->coop);
@@ -653,6 +667,96 @@ int gol_rule(gol_board* b, int* birth, int* survive) {
     *birth = (int)(b->rule & gol::kRuleMaskMax);
     *survive = (int)(b->rule >> 9);
     return GOL_OK;
+}
+
+// A Generations rule on the board (gol.h): the rule and the states per cell.  The alive plane never moves; the decay
+// buffers come and go with nstates.
+int gol_set_generations_rule(gol_board* b, int birth, int survive, int nstates) {
+    return with_board(b, [&] {
+        if (!gol::rule_masks_ok(birth, survive))
+            return fail(GOL_ERR_INVALID, "rule: birth and survive masks must lie in 0..0x1FF");
+        if (!gol::gen_states_ok(nstates)) return fail(GOL_ERR_INVALID, "rule: nstates must be 2..8");
+        const uint32_t rule = gol::rule_pack(birth, survive);
+        if (b->multi && (nstates != 2 || rule != gol::kRuleLifePacked))
+            return fail(GOL_ERR_UNSUPPORTED, "rule: a board on several GPUs runs B3/S23 at two states only (its strip "
+                                             "passes are the B3/S23 streaming kernels); the rule is unchanged");
+        if (b->multi) return GOL_OK;
+        GOL_RC(sync_bytes(b));  // as gol_set_rule: the bytes are the state from here on
+        if (nstates != b->nstates) {
+            // every dying cell becomes dead: fresh zeroed buffers where the size changes, the old ones zeroed where
+            // it does not; nothing of the board changes before every allocation has succeeded
+            const size_t need = gol_board::dec_bytes_of(b, nstates);
+            void* fresh[2] = {nullptr, nullptr};
+            const bool realloc = need != b->dec_bytes();
+            GOL_HIP(hipStreamSynchronize(b->stream));
+            if (realloc && need) {
+                for (void*& p : fresh) {
+                    const hipError_t e = hipMalloc(&p, need);
+                    if (e != hipSuccess) {
+                        p = nullptr;
+                        if (fresh[0]) (void)hipFree(fresh[0]);
+                        return fail(GOL_ERR_OOM, std::string("hipMalloc decay planes: ") + hipGetErrorString(e));
+                    }
+                }
+            }
+            if (realloc) {
+                for (int i = 0; i < 2; i++) {
+                    if (b->dec[i]) (void)hipFree(b->dec[i]);
+                    b->dec[i] = fresh[i];
+                }
+            }
+            b->nstates = nstates;
+            for (void* p : b->dec)
+                if (p) GOL_HIP(hipMemsetAsync(p, 0, need, b->stream));
+            GOL_HIP(hipStreamSynchronize(b->stream));
+        }
+        b->rule = rule;
+        return GOL_OK;
+    });
+}
+
+int gol_generations_rule(gol_board* b, int* birth, int* survive, int* nstates) {
+    if (!b) return fail(GOL_ERR_INVALID, "null board");
+    if (!birth || !survive || !nstates) return fail(GOL_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> g(b->mu);
+    *birth = (int)(b->rule & gol::kRuleMaskMax);
+    *survive = (int)(b->rule >> 9);
+    *nstates = b->nstates;
+    return GOL_OK;
+}
+
+int gol_set_states(gol_board* b, const uint8_t* states, int64_t len) {
+    return with_board(b, [&] {
+        if (!states || len != b->W * b->H) return fail(GOL_ERR_INVALID, "states length must be width*height");
+        for (int64_t i = 0; i < len; i++)
+            if (states[i] >= b->nstates) return fail(GOL_ERR_INVALID, "states: a byte is not below the board's nstates");
+        b->generation = 0;  // a new board, as after every other setter (gol.h)
+        if (b->multi) return set_cells_impl(b, states);  // two states: a state byte is a cell byte
+        const size_t n = (size_t)len;
+        DeviceBuffer staging;
+        GOL_RC(staging.alloc(n));
+        GOL_HIP(hipMemcpyAsync(staging.p, states, n, hipMemcpyHostToDevice, b->stream));
+        GOL_HIP(gol::launch_states_pack(staging.as<uint8_t>(), b->buf[b->cur], b->dec[b->cur], b->packed ? b->ilv : 0,
+                                        b->W, b->H, b->pitch, b->nstates, b->stream));
+        GOL_HIP(hipStreamSynchronize(b->stream));
+        return overwritten(b, false);
+    });
+}
+
+int gol_get_states(gol_board* b, uint8_t* states, int64_t len) {
+    return with_board(b, [&] {
+        if (!states || len != b->W * b->H) return fail(GOL_ERR_INVALID, "states length must be width*height");
+        if (b->multi) return readback_impl(b, states, b->W, 1);
+        GOL_RC(sync_bytes(b));
+        const size_t n = (size_t)len;
+        DeviceBuffer staging;
+        GOL_RC(staging.alloc(n));
+        GOL_HIP(gol::launch_states_unpack(b->buf[b->cur], b->dec[b->cur], staging.as<uint8_t>(), b->packed ? b->ilv : 0,
+                                          b->W, b->H, b->pitch, b->nstates, b->stream));
+        GOL_HIP(hipMemcpyAsync(states, staging.p, n, hipMemcpyDeviceToHost, b->stream));
+        GOL_HIP(hipStreamSynchronize(b->stream));
+        return check_valid(b);
+    });
 }
 
 int gol_device_count(int* n) {

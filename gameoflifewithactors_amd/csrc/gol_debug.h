@@ -24,6 +24,8 @@
  *   "rule_k" 0 | 1 | 2 | 4 | 8  the deepest pass of the rule-generic streaming pass (0: by layout; A/B)
  *   "rule_seg_rows" 0 | n       rows per wave segment of the rule-generic streaming pass (0: planned): small test
  *                               boards get several segments
+ *                               Both apply to the multi-plane streaming pass of a Generations board too:
+ *                               "rule_k" 4, 2, 1 force its depth, 8 is refused there (GOL_ERR_INVALID)
  * Unknown names return GOL_ERR_INVALID.
  */
 #ifndef GOL_DEBUG_H

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gol_generations.h"
 #include "gol_hash.h"
 #include "gol_internal.h"
 #include "gol_layout.h"
@@ -629,6 +630,211 @@ hipError_t launch_import_canonical(const uint64_t* in, int64_t W, int64_t rows, 
 hipError_t launch_set_points(void* board, int ilv, int64_t W, int64_t pitch, const int64_t* xy, int64_t n,
                              hipStream_t s) {
     hipLaunchKernelGGL(gol_set_points, dim3(grid1d(n)), dim3(256), 0, s, board, ilv, W, pitch, xy, n);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// Generations state of a board handle (gol_generations.h).  The alive plane is the board itself; the
+// dying cells sit beside it: packed boards P = gen_planes(nstates) planes of pitch * H words in the board's layout (d
+// as a binary number over them), byte boards one byte d per cell.
+
+// One generation of a byte board: gen_next_cell on the (alive byte, d byte) pair.  Only state-1 cells are neighbours.
+// Cells outside a bounded board are never read and never written.
+template <bool BOUNDED>
+__global__ __launch_bounds__(256) void gol_bytes_gen_step(const uint8_t* __restrict__ src, const uint8_t* __restrict__ dsrc,
+                                                           uint8_t* __restrict__ dst, uint8_t* __restrict__ ddst,
+                                                           int64_t W, int64_t H, int birth, int survive, int nstates) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= W * H) return;
+    const int64_t x = idx % W, y = idx / W;
+    int n = 0;
+#pragma unroll
+    for (int dy = -1; dy <= 1; dy++)
+#pragma unroll
+        for (int dx = -1; dx <= 1; dx++) {
+            if (!dx && !dy) continue;
+            int64_t nx = x + dx, ny = y + dy;
+            if (BOUNDED) {
+                if (nx < 0 || nx >= W || ny < 0 || ny >= H) continue;
+            } else {
+                nx = nx < 0 ? nx + W : (nx >= W ? nx - W : nx);
+                ny = ny < 0 ? ny + H : (ny >= H ? ny - H : ny);
+            }
+            n += src[nx + ny * W] != 0;
+        }
+    uint32_t alive = src[idx] != 0, d = dsrc[idx];
+    int s = 0;
+    gen_cell_convert(true, s, alive, d);
+    s = gen_next_cell(s, n, birth, survive, nstates);
+    gen_cell_convert(false, s, alive, d);
+    dst[idx] = (uint8_t)alive;
+    ddst[idx] = (uint8_t)d;
+}
+
+// state bytes -> board + decay: one thread per stored word (packed) or per cell (bytes)
+__global__ void gol_states_pack(const uint8_t* __restrict__ states, void* __restrict__ board, void* __restrict__ decay,
+                                int ilv, int64_t W, int64_t H, int64_t pitch, int planes) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (ilv > 0) {
+        const int64_t wpr = W / 32;
+        if (idx >= wpr * H) return;
+        const int64_t w = idx % wpr, y = idx / wpr;
+        const uint8_t* p = states + y * W;
+        uint32_t a = 0, dk[kGenPlanesMax] = {0, 0, 0};
+        for (int b = 0; b < 32; b++) {
+            int s = p[word_bit_cell(w, b, ilv)];
+            uint32_t alive, d;
+            gen_cell_convert(false, s, alive, d);
+            a |= alive << b;
+#pragma unroll
+            for (int k = 0; k < kGenPlanesMax; k++) dk[k] |= (d >> k & 1u) << b;
+        }
+        static_cast<uint32_t*>(board)[y * pitch + w] = a;
+#pragma unroll
+        for (int k = 0; k < kGenPlanesMax; k++)
+            if (k < planes) static_cast<uint32_t*>(decay)[k * pitch * H + y * pitch + w] = dk[k];
+    } else {
+        if (idx >= W * H) return;
+        int s = states[idx];
+        uint32_t alive, d;
+        gen_cell_convert(false, s, alive, d);
+        static_cast<uint8_t*>(board)[idx] = (uint8_t)alive;
+        if (planes) static_cast<uint8_t*>(decay)[idx] = (uint8_t)d;
+    }
+}
+
+// the state of cell (x, y) of a board handle (planes 0: a 2-state board, no decay)
+__device__ __forceinline__ int gen_cell_state_at(const void* board, const void* decay, int ilv, int64_t W, int64_t H,
+                                                 int64_t pitch, int planes, int64_t x, int64_t y) {
+    uint32_t alive, d = 0;
+    if (ilv > 0) {
+        int64_t word;
+        int bit;
+        cell_pos(x, ilv, word, bit);
+        const int64_t at = y * pitch + word;
+        alive = static_cast<const uint32_t*>(board)[at] >> bit & 1u;
+        for (int k = 0; k < planes; k++) d |= (static_cast<const uint32_t*>(decay)[k * pitch * H + at] >> bit & 1u) << k;
+    } else {
+        alive = static_cast<const uint8_t*>(board)[x + y * W] != 0;
+        if (planes) d = static_cast<const uint8_t*>(decay)[x + y * W];
+    }
+    int s = 0;
+    gen_cell_convert(true, s, alive, d);
+    return s;
+}
+
+// board + decay -> state bytes: one thread per stored word (packed) or per cell (bytes)
+__global__ void gol_states_unpack(const void* __restrict__ board, const void* __restrict__ decay,
+                                  uint8_t* __restrict__ states, int ilv, int64_t W, int64_t H, int64_t pitch,
+                                  int planes) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (ilv > 0) {
+        const int64_t wpr = W / 32;
+        if (idx >= wpr * H) return;
+        const int64_t w = idx % wpr, y = idx / wpr;
+        const uint32_t a = static_cast<const uint32_t*>(board)[y * pitch + w];
+        uint32_t dk[kGenPlanesMax] = {0, 0, 0};
+#pragma unroll
+        for (int k = 0; k < kGenPlanesMax; k++)
+            if (k < planes) dk[k] = static_cast<const uint32_t*>(decay)[k * pitch * H + y * pitch + w];
+        uint8_t* p = states + y * W;
+        for (int b = 0; b < 32; b++) {
+            uint32_t alive = a >> b & 1u, d = (dk[0] >> b & 1u) | (dk[1] >> b & 1u) << 1 | (dk[2] >> b & 1u) << 2;
+            int s = 0;
+            gen_cell_convert(true, s, alive, d);
+            p[word_bit_cell(w, b, ilv)] = (uint8_t)s;
+        }
+    } else {
+        if (idx >= W * H) return;
+        states[idx] = (uint8_t)gen_cell_state_at(board, decay, 0, W, H, pitch, planes, idx % W, idx / W);
+    }
+}
+
+// Canonical hash partial sum of the stacked board: chunk j of row y of state k's indicator is chunk j of row
+// (k - 1) H + y of a W x (nstates - 1) H board (gol_hash_packed's terms, summed over the states).  One thread per chunk.
+__global__ void gol_gen_hash(const void* __restrict__ board, const void* __restrict__ decay, int ilv, int64_t W,
+                             int64_t H, int64_t pitch, int planes, int nstates, unsigned long long* acc) {
+    const int64_t nc = (W + 63) / 64;
+    const int64_t n = nc * H;
+    uint64_t sum = 0;
+    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t j = idx % nc, y = idx / nc;
+        uint64_t v[kGenStatesMax - 1] = {0, 0, 0, 0, 0, 0, 0};  // v[k - 1]: the indicator chunk of state k
+        for (int i = 0; i < 64 && 64 * j + i < W; i++) {
+            const int s = gen_cell_state_at(board, decay, ilv, W, H, pitch, planes, 64 * j + i, y);
+#pragma unroll
+            for (int k = 1; k < kGenStatesMax; k++) v[k - 1] |= (uint64_t)(s == k) << i;
+        }
+#pragma unroll
+        for (int k = 1; k < kGenStatesMax; k++)
+            if (k < nstates) {
+                const uint64_t key = (uint64_t)(((int64_t)(k - 1) * H + y) * nc + j);
+                sum += fmix64(v[k - 1] ^ fmix64(key + 0x9E3779B97F4A7C15ULL));
+            }
+    }
+    block_add(sum, acc);
+}
+
+__global__ void gol_clear_points_decay(void* decay, int ilv, int64_t W, int64_t H, int64_t pitch, int planes,
+                                       const int64_t* xy, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t x = xy[2 * i], y = xy[2 * i + 1];
+    if (ilv > 0) {
+        int64_t word;
+        int bit;
+        cell_pos(x, ilv, word, bit);
+        for (int k = 0; k < planes; k++)
+            atomicAnd(&static_cast<uint32_t*>(decay)[k * pitch * H + y * pitch + word], ~(1u << bit));
+    } else {
+        static_cast<uint8_t*>(decay)[x + y * W] = 0;
+    }
+}
+
+hipError_t launch_bytes_gen_step(const uint8_t* src, const uint8_t* dsrc, uint8_t* dst, uint8_t* ddst, int64_t W,
+                                 int64_t H, bool bounded, int birth, int survive, int nstates, hipStream_t s) {
+    if (!rule_masks_ok(birth, survive) || !gen_states_ok(nstates) || nstates < 3 || !dsrc || !ddst)
+        return hipErrorInvalidValue;
+    if (bounded)
+        hipLaunchKernelGGL((gol_bytes_gen_step<true>), dim3(grid1d(W * H)), dim3(256), 0, s, src, dsrc, dst, ddst, W, H,
+                           birth, survive, nstates);
+    else
+        hipLaunchKernelGGL((gol_bytes_gen_step<false>), dim3(grid1d(W * H)), dim3(256), 0, s, src, dsrc, dst, ddst, W, H,
+                           birth, survive, nstates);
+    return hipGetLastError();
+}
+
+hipError_t launch_states_pack(const uint8_t* states, void* board, void* decay, int ilv, int64_t W, int64_t H,
+                              int64_t pitch, int nstates, hipStream_t s) {
+    if (!gen_states_ok(nstates) || (nstates > 2 && !decay)) return hipErrorInvalidValue;
+    const int64_t n = ilv > 0 ? W / 32 * H : W * H;
+    hipLaunchKernelGGL(gol_states_pack, dim3(grid1d(n)), dim3(256), 0, s, states, board, decay, ilv, W, H, pitch,
+                       gen_planes(nstates));
+    return hipGetLastError();
+}
+
+hipError_t launch_states_unpack(const void* board, const void* decay, uint8_t* states, int ilv, int64_t W, int64_t H,
+                                int64_t pitch, int nstates, hipStream_t s) {
+    if (!gen_states_ok(nstates) || (nstates > 2 && !decay)) return hipErrorInvalidValue;
+    const int64_t n = ilv > 0 ? W / 32 * H : W * H;
+    hipLaunchKernelGGL(gol_states_unpack, dim3(grid1d(n)), dim3(256), 0, s, board, decay, states, ilv, W, H, pitch,
+                       gen_planes(nstates));
+    return hipGetLastError();
+}
+
+hipError_t launch_gen_hash(const void* board, const void* decay, int ilv, int64_t W, int64_t H, int64_t pitch,
+                           int nstates, unsigned long long* acc, hipStream_t s) {
+    if (!gen_states_ok(nstates) || nstates < 3 || !decay) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(gol_gen_hash, dim3(grid_reduce((W + 63) / 64 * H)), dim3(256), 0, s, board, decay, ilv, W, H,
+                       pitch, gen_planes(nstates), nstates, acc);
+    return hipGetLastError();
+}
+
+hipError_t launch_clear_points_decay(void* decay, int ilv, int64_t W, int64_t H, int64_t pitch, int nstates,
+                                     const int64_t* xy, int64_t n, hipStream_t s) {
+    if (!gen_states_ok(nstates) || nstates < 3 || !decay) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(gol_clear_points_decay, dim3(grid1d(n)), dim3(256), 0, s, decay, ilv, W, H, pitch,
+                       gen_planes(nstates), xy, n);
     return hipGetLastError();
 }
 

@@ -46,7 +46,7 @@ inline bool gen_states_ok(int nstates) { return nstates >= kGenStatesMin && nsta
 constexpr int gen_planes(int nstates) { return nstates <= 2 ? 0 : nstates == 3 ? 1 : nstates <= 5 ? 2 : 3; }
 
 // The definition: the next state of a cell in state s with n (0..8) neighbours in state 1.
-inline int gen_next_cell(int s, int n, int birth, int survive, int nstates) {
+GOL_HD int gen_next_cell(int s, int n, int birth, int survive, int nstates) {
     if (s == 0) return birth >> n & 1;
     if (s == 1) return (survive >> n & 1) ? 1 : nstates > 2 ? 2 : 0;
     return s + 1 < nstates ? s + 1 : 0;
@@ -92,6 +92,18 @@ GOL_HD uint32_t gen_state_word(uint32_t alive, Plane&& plane, int planes, int k)
     uint32_t r = 0xffffffffu;
     for (int q = 0; q < planes; q++) r &= ((k - 1) >> q & 1) ? plane(q) : ~plane(q);
     return r;
+}
+
+// One cell between its state byte s (0 .. C - 1) and the encoding above: the alive bit and d = s - 1 of a dying cell
+// (0 for a dead or alive one).  to_state = false: s -> (alive, d); true: (alive, d) -> s.  The state I/O kernels of the
+// batch's planes aside, every conversion of a board handle goes through here (gol_formats.hip).
+GOL_HD void gen_cell_convert(bool to_state, int& s, uint32_t& alive, uint32_t& d) {
+    if (to_state) {
+        s = alive ? 1 : d ? (int)d + 1 : 0;
+    } else {
+        alive = s == 1 ? 1u : 0u;
+        d = s >= 2 ? (uint32_t)(s - 1) : 0u;
+    }
 }
 
 // "<rule>" or "<rule>/<n>", "<rule>/C<n>", "<rule>/G<n>" (any letter case), <rule> everything rule_parse accepts, n one

@@ -115,7 +115,32 @@ int rule_stream_max_k(int ilv);  // the deepest pass a layout runs by default
 hipError_t launch_rule_stream(const uint32_t* src, uint32_t* dst, int64_t W, int64_t H, int64_t pitch, int ilv, int k,
                               bool bounded, uint32_t rule, int64_t seg_opt, hipStream_t s);
 
+// ---- gol_gen_stream.hip: the multi-plane streaming pass (Generations rules, nstates 3..8, packed boards of any size and
+// layout; gol_rule_stream's plan).  src / dst: the alive plane; dsrc / ddst: the gen_planes(nstates) decay planes, plane
+// k at + k * pitch * H words.  k is 4, 2 or 1 (gol_gen_plan.h gen_stream_max_k: the deepest gol_step runs).
+hipError_t launch_gen_stream(const uint32_t* src, uint32_t* dst, const uint32_t* dsrc, uint32_t* ddst, int64_t W,
+                             int64_t H, int64_t pitch, int ilv, int k, bool bounded, uint32_t rule, int nstates,
+                             int64_t seg_opt, hipStream_t s);
+
 // ---- gol_formats.hip
+// A board handle's Generations state (gol_board.h): the alive plane / alive bytes `board` and beside it `decay` -- packed
+// boards (ilv > 0) gen_planes(nstates) planes of pitch * H words in the board's layout, byte boards (ilv 0) one byte
+// d per cell; decay may be null at nstates 2.
+// one generation of a byte board: gen_next_cell on the (alive byte, d byte) pair
+hipError_t launch_bytes_gen_step(const uint8_t* src, const uint8_t* dsrc, uint8_t* dst, uint8_t* ddst, int64_t W,
+                                 int64_t H, bool bounded, int birth, int survive, int nstates, hipStream_t s);
+// states[x + y * W] (every byte < nstates, checked by the caller) <-> the board and its decay
+hipError_t launch_states_pack(const uint8_t* states, void* board, void* decay, int ilv, int64_t W, int64_t H,
+                              int64_t pitch, int nstates, hipStream_t s);
+hipError_t launch_states_unpack(const void* board, const void* decay, uint8_t* states, int ilv, int64_t W, int64_t H,
+                                int64_t pitch, int nstates, hipStream_t s);
+// adds the canonical hash partial of the stacked W x (nstates - 1) H board (rows [(k - 1) H, k H) the indicator of
+// state k) into *acc; nstates 3..8
+hipError_t launch_gen_hash(const void* board, const void* decay, int ilv, int64_t W, int64_t H, int64_t pitch,
+                           int nstates, unsigned long long* acc, hipStream_t s);
+// the cells listed as (x, y) pairs lose their decay bits (gol_place_rle makes them state 1)
+hipError_t launch_clear_points_decay(void* decay, int ilv, int64_t W, int64_t H, int64_t pitch, int nstates,
+                                     const int64_t* xy, int64_t n, hipStream_t s);
 hipError_t launch_bytes_step(const uint8_t* src, uint8_t* dst, int64_t W, int64_t H, bool bounded, hipStream_t s);
 // the same step under any life-like rule (birth, survive: the 9-bit masks of gol_rule.h)
 hipError_t launch_bytes_rule_step(const uint8_t* src, uint8_t* dst, int64_t W, int64_t H, bool bounded, int birth,

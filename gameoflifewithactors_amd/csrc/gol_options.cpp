@@ -113,6 +113,8 @@ const Option kOptions[] = {
     {"rule_k", kDebug, get<&O::rule_k>,
      [](gol_board* b, int64_t v) {
          if (v != 0 && v != 1 && v != 2 && v != 4 && v != 8) return fail(GOL_ERR_INVALID, "rule_k must be 0, 1, 2, 4 or 8");
+         if (v == 8 && b->nstates > 2)
+             return fail(GOL_ERR_INVALID, "rule_k 8: a Generations board's streaming pass runs 4, 2 or 1 generations per pass");
          return set_any<&O::rule_k>(b, v);
      }},
     {"rule_seg_rows", kDebug, get<&O::rule_seg_rows>,

@@ -4,6 +4,7 @@
 #include <algorithm>
 
 #include "gol_board.h"
+#include "gol_gen_plan.h"
 
 using gol::check_valid;
 using gol::fail;
@@ -235,7 +236,11 @@ int run_resident(gol_board* b, int64_t gens) {
 int run_bytes(gol_board* b, int64_t gens) {
     const bool rule = b->rule_family();
     return ping_pong(b, &b->cur, gens, at_most(1), [&](int64_t) {
-        if (rule)
+        if (b->nstates > 2)  // a Generations board: the (alive byte, d byte) pair, both ping-ponging
+            GOL_HIP(gol::launch_bytes_gen_step(b->cells(b->cur), b->dec_cells(b->cur), b->cells(b->cur ^ 1),
+                                               b->dec_cells(b->cur ^ 1), b->W, b->H, b->boundary == GOL_BOUNDED,
+                                               (int)(b->rule & 0x1FF), (int)(b->rule >> 9), b->nstates, b->stream));
+        else if (rule)
             GOL_HIP(gol::launch_bytes_rule_step(b->cells(b->cur), b->cells(b->cur ^ 1), b->W, b->H,
                                                 b->boundary == GOL_BOUNDED, (int)(b->rule & 0x1FF), (int)(b->rule >> 9),
                                                 b->stream));
@@ -256,6 +261,24 @@ int run_rule_stream(gol_board* b, int64_t gens) {
                          GOL_HIP(gol::launch_rule_stream(b->words(b->cur), b->words(b->cur ^ 1), b->W, b->H, b->pitch,
                                                          b->ilv, (int)g, b->boundary == GOL_BOUNDED, b->rule,
                                                          b->opt.rule_seg_rows, b->stream));
+                         return GOL_OK;
+                     });
+}
+
+// the multi-plane streaming pass of a Generations board: passes of gen_stream_max_k generations (gol_gen_plan.h;
+// "rule_k" 4, 2, 1 force a depth), then the binary remainder; the decay planes ping-pong with the alive plane
+int run_gen_stream(gol_board* b, int64_t gens) {
+    if (b->opt.rule_k == 8)
+        return fail(GOL_ERR_UNSUPPORTED, "rule_k 8: the multi-plane streaming pass of a Generations board runs 4, 2 or 1 "
+                                         "generations per pass");
+    const int cap = b->opt.rule_k ? b->opt.rule_k
+                                  : gol::gen_stream_max_k(b->ilv, gol::gen_planes(b->nstates), b->boundary == GOL_BOUNDED);
+    return ping_pong(b, &b->cur, gens, [cap](int64_t left) { return (int64_t)gol::gen_stream_largest_k(left, cap); },
+                     [&](int64_t g) {
+                         GOL_HIP(gol::launch_gen_stream(b->words(b->cur), b->words(b->cur ^ 1), b->dec_words(b->cur),
+                                                        b->dec_words(b->cur ^ 1), b->W, b->H, b->pitch, b->ilv, (int)g,
+                                                        b->boundary == GOL_BOUNDED, b->rule, b->nstates,
+                                                        b->opt.rule_seg_rows, b->stream));
                          return GOL_OK;
                      });
 }
@@ -285,6 +308,7 @@ int step_impl(gol_board* b, int64_t gens) {
     const gol::PassChoice c = gol::choose_pass(b, gens);
     b->last_pass = c.pass;
     if (b->rag_state != rag_state_of(c.pass)) GOL_RC(sync_bytes(b));
+    if (c.pass == gol::kPassGenStream) return run_gen_stream(b, gens);
     switch (c.pass) {
         case Pass::Multi: return b->multi->step(gens, &b->generation);
         case Pass::Wave: return run_wave(b, gens);
@@ -319,6 +343,9 @@ int gol_pass_timing(gol_board* b, int n, double* interior_us, double* wait_us, d
         if (n != parts || !interior_us || !wait_us || !edge_us)
             return fail(GOL_ERR_INVALID, "n must equal gol_num_parts and the arrays must be non-null");
         if (b->multi) return b->multi->timed_pass(interior_us, wait_us, edge_us, &b->generation);
+        if (b->nstates > 2)
+            return fail(GOL_ERR_UNSUPPORTED, "pass timing measures the B3/S23 streaming pass: this board runs a "
+                                             "Generations rule (gol_set_generations_rule; gol_step_timed times any)");
         if (b->rule_family())
             return fail(GOL_ERR_UNSUPPORTED, "pass timing measures the B3/S23 streaming pass: this board runs another "
                                              "rule (gol_set_rule) or the rule family's passes (gol_step_timed times any)");

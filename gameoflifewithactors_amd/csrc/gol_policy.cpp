@@ -223,8 +223,13 @@ void board_layout(gol_board* b, int nparts, int tblock_k, int ilv) {
 // has three passes: the single-wave kernel with the rule table where it applies, the rule-generic streaming pass
 // (gol_rule_step.hip) on every other packed board whatever its layout, and the per-generation byte step under the rule
 // on the byte boards left.  The lanes, cooperative, LDS-resident, ragged and pipelined passes are B3/S23 only.
+//
+// A Generations board (nstates > 2, gol_set_generations_rule; single boards only) has two passes whatever its rule
+// and size: the multi-plane streaming pass (gol_gen_stream.hip) on every packed board, and the per-generation byte step
+// on the (alive byte, d byte) pair on every byte board.  The single-wave pass is not taken there.
 PassChoice choose_pass(const gol_board* b, int64_t gens) {
     if (b->multi) return {Pass::Multi, 0};
+    if (b->nstates > 2) return {b->packed ? kPassGenStream : Pass::Bytes, 0};
     if (use_wave_resident(b)) return {Pass::Wave, 0};
     if (b->rule_family()) return {b->packed ? Pass::RuleStream : Pass::Bytes, 0};
     if (use_lanes(b, gens)) return {Pass::Lanes, 0};

@@ -132,8 +132,9 @@ def run(
     With ``period_s`` a timer ticks like L38-40 (reference: ProcessorCount * 70 ms).  ``num_gpus`` > 1
     spreads the board over that many GPUs of this process (row strips; needs a width divisible by 32).
     ``emit="view"`` posts one ``Board.render_view`` frame per tick for ``view = (x, y, scale, out_w, out_h)`` in
-    ``view_mode`` (VIEW_ANY / VIEW_DENSITY) instead of the whole board.  ``rule``: the life-like rule every tick runs
-    under, as ``Board.set_rule`` takes it (the reference's is B3/S23)."""
+    ``view_mode`` (VIEW_ANY / VIEW_DENSITY) instead of the whole board.  ``rule``: the life-like or Generations
+    rule every tick runs under, as ``Board.set_rule`` takes it ("B36/S23", "B2/S/3"; the reference's is B3/S23).  Under
+    a Generations rule the frames show the alive cells (state 1)."""
     if seed is None:
         seed = int(time.time_ns() // 100) & 0xFFFFFFFF  # .NET ticks are 100 ns; `int` truncates to 32 bits
         seed = seed - (1 << 32) if seed >= (1 << 31) else seed

@@ -370,6 +370,30 @@ int gol_generations_set_states(gol_batch* b, int64_t first, int64_t n, const uin
 int gol_generations_get_states(gol_batch* b, int64_t first, int64_t n, uint8_t* states, int64_t len);
 int gol_generations_parse(const char* text, int* birth, int* survive, int* nstates);
 int gol_generations_format(int birth, int survive, int nstates, char* out, int64_t len);
+/* Generations rules on a single board (gol_board): the transition above at any board size.  A new board
+ * has nstates 2.  The alive cells stay what every cell call of this header reads and writes: gol_get_cells,
+ * gol_get_region, gol_render_gray8, gol_view_counts / gol_render_view, gol_population, gol_save_packed, the RLE text
+ * see state 1 alone; gol_set_cells, gol_load_packed, both seeds and gol_clear write states 0 and 1 only (a dying cell
+ * becomes dead); gol_place_rle makes the cells it places state 1.  Snapshots carry the alive cells only.
+ *   gol_set_generations_rule  masks as for gol_set_rule, nstates in 2..8; anything else is GOL_ERR_INVALID and nothing
+ *     changes.  The same nstates as the board has: only birth and survive change, dying cells stay.  Another nstates:
+ *     every dying cell becomes dead, the alive cells and the generation counter are untouched (nstates 2: the board is
+ *     a life-like board again and takes the passes it took).  GOL_ERR_OOM leaves the board as it was, nstates and rule
+ *     included.  A board on several GPUs takes B3/S23 at nstates 2 only (GOL_ERR_UNSUPPORTED, board unchanged).
+ *     gol_set_rule on a Generations board changes birth and survive and keeps nstates and the dying cells.
+ *   gol_generations_rule  all three; gol_rule still returns the two masks.  A null output is GOL_ERR_INVALID.
+ *   gol_set_states / gol_get_states  one byte per cell holding the state, len == width * height.  A byte >= nstates is
+ *     GOL_ERR_INVALID before any device work, board untouched.  set_states resets the generation counter, like every
+ *     setter.  Both work on a 2-state board, with states 0 and 1.
+ *   On a board with nstates > 2: gol_hash is the gol_hash of a single width x (nstates - 1) * height board whose rows
+ *     [(k - 1) height, k height) are the indicator of state k (what gol_batch_hashes gives a Generations batch);
+ *     gol_pass_timing returns GOL_ERR_UNSUPPORTED.  Every bit-packed board runs the multi-plane streaming pass
+ *     (csrc/gol_gen_stream.hip: up to 4 generations per pass over the board, any size, any layout), every byte board
+ *     one launch per generation. */
+int gol_set_generations_rule(gol_board* b, int birth, int survive, int nstates);
+int gol_generations_rule(gol_board* b, int* birth, int* survive, int* nstates);
+int gol_set_states(gol_board* b, const uint8_t* states, int64_t len);
+int gol_get_states(gol_board* b, uint8_t* states, int64_t len);
 /* The ensemble's cycle census: for every board, after how many generations it enters a cycle and of
  * what period, one launch, one wavefront per board, the search in that wave's registers.
  *   Definition: B_0 = board i's current cells, B_(t+1) = the next generation of B_t under the batch's rule and boundary;

@@ -255,6 +255,28 @@ class Board {
         check(gol_rule_format(birth, survive, text, sizeof text), "gol_rule_format");
         return text;
     }
+    // Generations rules ("B2/S345/4", "B2/S/C3"; two fields: two states): nstates 2..8 states per cell, the alive
+    // cells where they were, state bytes through setStates / getStates.  Boards on several GPUs stay at two states.
+    Board& setGenerationsRule(const std::string& rule) {
+        int birth = 0, survive = 0, nstates = 2;
+        check(gol_generations_parse(rule.c_str(), &birth, &survive, &nstates), "gol_generations_parse");
+        check(gol_set_generations_rule(b_, birth, survive, nstates), "gol_set_generations_rule");
+        return *this;
+    }
+    int nstates() const {
+        int birth = 0, survive = 0, n = 2;
+        check(gol_generations_rule(b_, &birth, &survive, &n), "gol_generations_rule");
+        return n;
+    }
+    Board& setStates(const std::vector<uint8_t>& states) {  // states[x + y*W], each below nstates()
+        check(gol_set_states(b_, states.data(), (int64_t)states.size()), "gol_set_states");
+        return *this;
+    }
+    std::vector<uint8_t> getStates() const {
+        std::vector<uint8_t> s((size_t)(w_ * h_));
+        check(gol_get_states(b_, s.data(), (int64_t)s.size()), "gol_get_states");
+        return s;
+    }
     Board& step(int64_t generations = 1) {
         check(gol_step(b_, generations), "gol_step");
         return *this;
