@@ -97,6 +97,10 @@ enum class Pass { None, Wave, Lanes, Coop, CoopRagged, Ring, StreamRagged, Resid
 // 4.15).  It is a named value of the type beside the enumerator list, not a thirteenth enumerator: the list as it
 // stands above is what tests/test_board_rules_host.py reads out of this file.
 constexpr Pass kPassGenStream = static_cast<Pass>(12);
+// Values 13 and 14, in the same way: the rule-generic and the multi-plane streaming pass on the whole-word scratch
+// rows of a ragged byte board (gol_rule_stream_ragged, gol_gen_stream_ragged).
+constexpr Pass kPassRuleRagged = static_cast<Pass>(13);
+constexpr Pass kPassGenRagged = static_cast<Pass>(14);
 
 extern const int64_t kCoopMaxCells;               // gol_policy.cpp
 constexpr int kCoopFlagWords = 1024;              // bands of one launch at most (one per CU) ...
@@ -144,6 +148,11 @@ struct BoardOptions {
     int64_t rule_seg_rows = 0;                // "rule_seg_rows" (gol_debug.h): rows per wave segment of the rule-generic
                                               // streaming pass (0 = planned)
     int rule_k = 0;                           // "rule_k" (gol_debug.h): its deepest pass, 8, 4, 2 or 1 (0 = by layout)
+    int rule_ragged = 1;                      // "rule_ragged": ragged byte boards under a life-like or Generations rule
+                                              // on the streaming passes through whole-word scratch rows: 1 = boards of
+                                              // more than 128 * 256 cells (Generations: 2^22) on calls of >= 4
+                                              // generations, 2 = every board at least 64 cells wide on every call,
+                                              // 0 = never (the byte step)
 };
 
 }  // namespace gol
@@ -175,8 +184,10 @@ struct gol_board {
     int64_t rag_words = 0;                  // capacity of each rag buffer
     // Ragged byte boards between gol_step calls of the multi-generation passes keep their state in the scratch rows:
     // 0 = the bytes (cells(cur)) are current; 1 = rag[rag_cur] holds it in the streaming pass's rows (rag_pitch words),
-    // 2 = in the cooperative pass's rows, 3 = in ring rows (gol_formats.hip, layout rag_ilv).  Every other access first
-    // brings the bytes up to date (sync_bytes).
+    // 2 = in the cooperative pass's rows, 3 = in ring rows (gol_formats.hip, layout rag_ilv), 4 = a Generations board:
+    // the alive plane in the streaming pass's rows and behind it, at + (1 + k) * rag_pitch * H words, decay plane k
+    // (the ragged rule passes; a two-state board under a rule is state 1).  Every other access first
+    // brings the bytes -- state 4: the alive and the d bytes -- up to date (sync_bytes).
     int rag_state = 0;
     int rag_cur = 0;
     int64_t rag_pitch = 0;

@@ -78,6 +78,9 @@ int sync_bytes(gol_board* b) {
                                         b->boundary == GOL_TORUS, b->stream));
     else
         GOL_HIP(gol::launch_unpack_ragged(b->rag[b->rag_cur], b->cells(b->cur), b->W, b->H, b->rag_pitch, b->stream));
+    if (b->rag_state == 4)  // a Generations board: the decay planes behind the alive rows become the d bytes
+        GOL_HIP(gol::launch_unpack_ragged_decay(b->rag[b->rag_cur] + b->rag_pitch * b->H, b->dec_cells(b->cur), b->W, b->H,
+                                                b->rag_pitch, gol::gen_planes(b->nstates), b->stream));
     b->rag_state = 0;
     return GOL_OK;
 }
@@ -653,7 +656,8 @@ int gol_set_rule(gol_board* b, int birth, int survive) {
         if (b->multi && rule != gol::kRuleLifePacked)
             return fail(GOL_ERR_UNSUPPORTED, "rule: a board on several GPUs runs B3/S23 only (its strip passes are the "
                                              "B3/S23 streaming kernels); the rule is unchanged");
-        // no ragged multi-generation pass runs under another rule: the bytes are the state from here on
+        // the scratch rows of one rule's passes are not another's (B3/S23's may be ring or cooperative rows): the bytes
+        // are the state from here on
         if (!b->multi) GOL_RC(sync_bytes(b));
         b->rule = rule;
         return GOL_OK;

@@ -15,7 +15,8 @@
  *   "last_pass"                 (read-only) the pass the last gol_step / gol_step_timed call took, as gol::Pass
  *                               (gol_board.h): 0 none yet, 1 single-wave, 2 rows-on-lanes, 3 cooperative, 4 cooperative on
  *                               a ragged board's scratch rows, 5 block (ring) rows, 6 ragged streaming, 7 LDS-resident,
- *                               8 byte step, 9 streaming, 10 multi-part, 11 rule-generic streaming
+ *                               8 byte step, 9 streaming, 10 multi-part, 11 rule-generic streaming,
+ *                               12 multi-plane streaming (Generations), 13 / 14 those two on a ragged board's scratch rows
  *   "rule_table" 0 | 1          1: a B3/S23 board runs the passes of the rule family too (single-wave with the rule
  *                               table, rule-generic streaming, byte step under the rule), as any other rule always
  *                               does.  Results are identical: the knob is what lets the rule arithmetic be checked
@@ -25,7 +26,8 @@
  *   "rule_seg_rows" 0 | n       rows per wave segment of the rule-generic streaming pass (0: planned): small test
  *                               boards get several segments
  *                               Both apply to the multi-plane streaming pass of a Generations board too:
- *                               "rule_k" 4, 2, 1 force its depth, 8 is refused there (GOL_ERR_INVALID)
+ *                               "rule_k" 4, 2, 1 force its depth, 8 is refused there (GOL_ERR_INVALID); and to both
+ *                               passes on a ragged board's scratch rows
  * Unknown names return GOL_ERR_INVALID.
  */
 #ifndef GOL_DEBUG_H

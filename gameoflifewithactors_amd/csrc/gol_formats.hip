@@ -140,6 +140,58 @@ __global__ __launch_bounds__(256) void gol_unpack_ragged(const uint32_t* __restr
     }
 }
 
+// The decay bytes of a ragged Generations byte board (d = state - 1 of a dying cell, 0 otherwise) <-> P bit planes of
+// such scratch rows beside the alive rows (the multi-plane streaming pass on ragged boards): plane k
+// holds bit k of d, at + k * plane words.  The same chunks, loads and ballots as above, one ballot per plane.
+template <int P>
+__global__ __launch_bounds__(256) void gol_pack_ragged_decay(const uint8_t* __restrict__ decay,
+                                                              uint32_t* __restrict__ words, int64_t W, int64_t H,
+                                                              int64_t pitch, int64_t plane) {
+    int64_t y, w0;
+    if (!ragged_chunk(pitch, H, y, w0)) return;
+    const int lane = threadIdx.x & 63;
+    const __amdgpu_buffer_rsrc_t row =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(decay + y * W), (short)0, (int)W, 0x00020000);
+    uint8_t v[kChunkWords / 2];
+#pragma unroll
+    for (int i = 0; i < kChunkWords / 2; i++)
+        v[i] = __builtin_amdgcn_raw_buffer_load_b8(row, (int)((w0 + 2 * i) * 32) + lane, 0, 0);
+#pragma unroll
+    for (int k = 0; k < P; k++) {
+        uint32_t mine = 0;  // word w0 + lane of plane k
+#pragma unroll
+        for (int i = 0; i < kChunkWords / 2; i++) {
+            const uint64_t m = __ballot((v[i] >> k & 1) != 0);
+            mine = lane == 2 * i ? (uint32_t)m : (lane == 2 * i + 1 ? (uint32_t)(m >> 32) : mine);
+        }
+        if (w0 + lane < pitch) words[k * plane + y * pitch + w0 + lane] = mine;
+    }
+}
+template <int P>
+__global__ __launch_bounds__(256) void gol_unpack_ragged_decay(const uint32_t* __restrict__ words,
+                                                                uint8_t* __restrict__ decay, int64_t W, int64_t H,
+                                                                int64_t pitch, int64_t plane) {
+    const int64_t nw = (W + 31) / 32;
+    int64_t y, w0;
+    if (!ragged_chunk(nw, H, y, w0)) return;
+    const int lane = threadIdx.x & 63;
+    uint32_t mine[P];
+#pragma unroll
+    for (int k = 0; k < P; k++) mine[k] = w0 + lane < nw ? words[k * plane + y * pitch + w0 + lane] : 0u;
+    const __amdgpu_buffer_rsrc_t row = __builtin_amdgcn_make_buffer_rsrc(decay + y * W, (short)0, (int)W, 0x00020000);
+#pragma unroll
+    for (int i = 0; i < kChunkWords / 2; i++) {
+        uint32_t d = 0;
+#pragma unroll
+        for (int k = 0; k < P; k++) {
+            const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)mine[k], 2 * i);
+            const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)mine[k], 2 * i + 1);
+            d |= (((lane < 32 ? lo : hi) >> (lane & 31)) & 1u) << k;
+        }
+        __builtin_amdgcn_raw_buffer_store_b8((uint8_t)d, row, (int)((w0 + 2 * i) * 32) + lane, 0, 0);
+    }
+}
+
 // ---- Ring rows of a ragged TORUS board (DESIGN.md 4.1 "Ragged rows: ring rows").  A row of W cells (W not a multiple
 // of 32) is a ring (GameOfLifeDriver.fs:21-25).  It is stored as an ALIGNED row of Wp = 64 * ceil((W + 2 * 64) / 64)
 // cells in the packed layout `ilv` (1 or 2): ring position u holds cell x = (u - 64) mod W, so u in [64, 64 + W) are
@@ -526,6 +578,32 @@ hipError_t launch_unpack_ragged(const uint32_t* words, uint8_t* cells, int64_t W
     if (pitch < (W + 31) / 32 || (pitch + kChunkWords) * 32 >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(gol_unpack_ragged, dim3(ragged_blocks((W + 31) / 32, H)), dim3(256), 0, s, words, cells, W, H,
                        pitch);
+    return hipGetLastError();
+}
+
+hipError_t launch_pack_ragged_decay(const uint8_t* decay, uint32_t* words, int64_t W, int64_t H, int64_t pitch,
+                                    int planes, hipStream_t s) {
+    if (pitch < (W + 31) / 32 || (pitch + kChunkWords) * 32 >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
+    const dim3 grid(ragged_blocks(pitch, H)), block(256);
+    switch (planes) {
+        case 1: hipLaunchKernelGGL(gol_pack_ragged_decay<1>, grid, block, 0, s, decay, words, W, H, pitch, pitch * H); break;
+        case 2: hipLaunchKernelGGL(gol_pack_ragged_decay<2>, grid, block, 0, s, decay, words, W, H, pitch, pitch * H); break;
+        case 3: hipLaunchKernelGGL(gol_pack_ragged_decay<3>, grid, block, 0, s, decay, words, W, H, pitch, pitch * H); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_unpack_ragged_decay(const uint32_t* words, uint8_t* decay, int64_t W, int64_t H, int64_t pitch,
+                                      int planes, hipStream_t s) {
+    if (pitch < (W + 31) / 32 || (pitch + kChunkWords) * 32 >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
+    const dim3 grid(ragged_blocks((W + 31) / 32, H)), block(256);
+    switch (planes) {
+        case 1: hipLaunchKernelGGL(gol_unpack_ragged_decay<1>, grid, block, 0, s, words, decay, W, H, pitch, pitch * H); break;
+        case 2: hipLaunchKernelGGL(gol_unpack_ragged_decay<2>, grid, block, 0, s, words, decay, W, H, pitch, pitch * H); break;
+        case 3: hipLaunchKernelGGL(gol_unpack_ragged_decay<3>, grid, block, 0, s, words, decay, W, H, pitch, pitch * H); break;
+        default: return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 

@@ -20,6 +20,9 @@
 //
 // nstates is a kernel argument (its C - 2 masks are scalars), P a template parameter.  Depths are 4, 2 and 1; which one
 // gol_step runs per (M, P, boundary) is gen_stream_max_k (gol_gen_plan.h).
+//
+// gol_gen_stream_ragged below is the same pass on the whole-word scratch rows and decay planes of a ragged byte board
+// (width not a multiple of 32; gol_policy.cpp use_rule_ragged).
 #include "gol_internal.h"
 #include "gol_bitlogic.h"
 #include "gol_generations.h"
@@ -249,6 +252,110 @@ __global__ __launch_bounds__(64 * kRuleWavesPerBlock) void gol_gen_stream(
     }
 }
 
+// gol_gen_stream at M = 1 on the scratch rows of a ragged byte board W cells wide: every plane H rows of plan.nblocks =
+// pitch = ceil(W / 32) words, the last one partial with zero pad bits, loaded, masked and stored as in
+// gol_rule_stream_ragged (gol_rule_step.hip; gol_rule_plan.h "Ragged rows"): a lane's decay words are the
+// same 32 ring cells as its alive word, and the partial word's lane stores the real cells of every plane.  A kernel of
+// its own beside gol_gen_stream for that kernel's reason.
+template <int K, int P, bool BOUNDED>
+__global__ __launch_bounds__(64 * kRuleWavesPerBlock) void gol_gen_stream_ragged(
+    const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, const uint32_t* __restrict__ dsrc,
+    uint32_t* __restrict__ ddst, RulePlan plan, int64_t pitch, int64_t plane, uint32_t rule, int nstates, int64_t W) {
+    constexpr int M = 1;
+    const int lane = threadIdx.x & 63;
+    const int64_t wave =
+        (int64_t)blockIdx.x * kRuleWavesPerBlock + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (wave >= plan.nwaves) return;
+    const RuleWave w = rule_wave(plan, wave);
+    int64_t lblk, sblk;
+    const bool lane_ld = rule_lane_load(plan, w, lane, &lblk) || !BOUNDED;  // (a torus lane always loads)
+    const bool lane_st = rule_lane_store(plan, w, lane, &sblk);
+    const uint32_t lanemask = BOUNDED ? rule_ragged_level_mask(plan, w, lane, W) : 0xffffffffu;
+    const uint32_t stmask = rule_ragged_store_mask(plan, w, lane, W);
+    RaggedWindow rw{};     // torus only: the lane's window, and whether any lane of this wave assembles its word
+    bool shifted = false;  // (wave-uniform)
+    if constexpr (!BOUNDED) {
+        rw = rule_ragged_window(w, lane, W);
+        shifted = __ballot(!rule_ragged_plain(rw)) != 0;
+    }
+    const int64_t H = plan.H;
+    const int64_t ybase = w.r0 - K;  // the row step 0 loads, before the modulo
+    const GenMasks g = gen_masks(nstates);
+
+    // step t's row: loaded only inside the stream, (bounded) inside the board and by lanes inside the board
+    int64_t ywrap = BOUNDED ? ybase : rule_mod(ybase, H);  // the next row to load (torus: wrapped)
+    auto load_row = [&](int64_t t, uint32_t (&v)[M], uint32_t (&dv)[P][M]) {
+#pragma unroll
+        for (int j = 0; j < M; j++) {
+            v[j] = 0;
+#pragma unroll
+            for (int k = 0; k < P; k++) dv[k][j] = 0;
+        }
+        const bool row_ok = t < w.steps && (!BOUNDED || (ywrap >= 0 && ywrap < H));
+        if constexpr (BOUNDED) {
+            if (row_ok && lane_ld) {
+                const int64_t at = ywrap * pitch + lblk;
+                v[0] = src[at];
+#pragma unroll
+                for (int k = 0; k < P; k++) dv[k][0] = dsrc[k * plane + at];
+            }
+        } else if (row_ok) {
+            const int64_t at = ywrap * pitch;
+            if (shifted) {
+                v[0] = rule_ragged_load(src + at, rw);
+#pragma unroll
+                for (int k = 0; k < P; k++) dv[k][0] = rule_ragged_load(dsrc + k * plane + at, rw);
+            } else {
+                v[0] = src[at + rw.word];
+#pragma unroll
+                for (int k = 0; k < P; k++) dv[k][0] = dsrc[k * plane + at + rw.word];
+            }
+        }
+        ywrap++;
+        if (!BOUNDED && ywrap == H) ywrap = 0;
+    };
+
+    GenWindows<K, M, P, BOUNDED> win;
+    win.clear();
+    uint32_t nxt[kRuleTripRows][M], nxd[kRuleTripRows][P][M];
+#pragma unroll
+    for (int r = 0; r < kRuleTripRows; r++) load_row(r, nxt[r], nxd[r]);
+
+    const int64_t nstore = w.r1 - w.r0;
+#pragma nounroll
+    for (int64_t T = 0; T < w.trips; T++) {
+        uint32_t cur[kRuleTripRows][M], cud[kRuleTripRows][P][M];
+#pragma unroll
+        for (int r = 0; r < kRuleTripRows; r++)
+#pragma unroll
+            for (int j = 0; j < M; j++) {
+                cur[r][j] = nxt[r][j];
+#pragma unroll
+                for (int k = 0; k < P; k++) cud[r][k][j] = nxd[r][k][j];
+            }
+        const int64_t t0 = T * kRuleTripRows;
+#pragma unroll
+        for (int r = 0; r < kRuleTripRows; r++) load_row(t0 + kRuleTripRows + r, nxt[r], nxd[r]);
+        __builtin_amdgcn_sched_barrier(0);  // the prefetch stays at the top of the trip
+        // the last level's output of step t is row r0 - 2 K + t
+        auto finish = [&](int64_t t, uint32_t (&x)[M], uint32_t (&dx)[P][M]) {
+            const int64_t o = t - 2 * K;
+            if (o >= 0 && o < nstore && lane_st) {
+                const int64_t at = (w.r0 + o) * pitch + sblk;
+                dst[at] = x[0] & stmask;
+#pragma unroll
+                for (int k = 0; k < P; k++) ddst[k * plane + at] = dx[k][0] & stmask;
+            }
+        };
+        win.template step<0>(cur[0], cud[0], rule, g, lanemask, ybase + t0 - 1, H);
+        finish(t0, cur[0], cud[0]);
+        win.template step<1>(cur[1], cud[1], rule, g, lanemask, ybase + t0, H);
+        finish(t0 + 1, cur[1], cud[1]);
+        win.template step<2>(cur[2], cud[2], rule, g, lanemask, ybase + t0 + 1, H);
+        finish(t0 + 2, cur[2], cud[2]);
+    }
+}
+
 struct GenLaunch {
     const uint32_t *src, *dsrc;
     uint32_t *dst, *ddst;
@@ -257,7 +364,30 @@ struct GenLaunch {
     uint32_t rule;
     int nstates;
     hipStream_t s;
+    int64_t ragged_w = 0;
 };
+
+template <int K, int P>
+hipError_t launch_kp_ragged(const GenLaunch& a) {
+    const dim3 grid((unsigned)rule_stream_grid(a.plan)), block(64 * kRuleWavesPerBlock);
+    if (a.plan.bounded)
+        hipLaunchKernelGGL((gol_gen_stream_ragged<K, P, true>), grid, block, 0, a.s, a.src, a.dst, a.dsrc, a.ddst,
+                           a.plan, a.pitch, a.plane, a.rule, a.nstates, a.ragged_w);
+    else
+        hipLaunchKernelGGL((gol_gen_stream_ragged<K, P, false>), grid, block, 0, a.s, a.src, a.dst, a.dsrc, a.ddst,
+                           a.plan, a.pitch, a.plane, a.rule, a.nstates, a.ragged_w);
+    return hipGetLastError();
+}
+
+template <int P>
+hipError_t launch_p_ragged(const GenLaunch& a) {
+    switch (a.plan.K) {
+        case 4: return launch_kp_ragged<4, P>(a);
+        case 2: return launch_kp_ragged<2, P>(a);
+        case 1: return launch_kp_ragged<1, P>(a);
+    }
+    return hipErrorInvalidValue;
+}
 
 template <int K, int M, int P>
 hipError_t launch_kmp(const GenLaunch& a) {
@@ -306,6 +436,24 @@ hipError_t launch_gen_stream(const uint32_t* src, uint32_t* dst, const uint32_t*
         case 1: return launch_m<1>(a);
         case 2: return launch_m<2>(a);
         case 4: return launch_m<4>(a);
+    }
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_gen_stream_ragged(const uint32_t* src, uint32_t* dst, const uint32_t* dsrc, uint32_t* ddst, int64_t W,
+                                    int64_t H, int k, bool bounded, uint32_t rule, int nstates, int64_t seg_opt,
+                                    hipStream_t s) {
+    if (!rule_ragged_ok(W) || H < 1 || !rule_packed_ok(rule) || (k != 4 && k != 2 && k != 1) ||
+        !gen_states_ok(nstates) || nstates < 3 || !dsrc || !ddst)
+        return hipErrorInvalidValue;
+    const int64_t nw = rule_ragged_words(W);
+    GenLaunch a{src, dsrc, dst, ddst, rule_stream_plan(nw * 32, H, 1, k, bounded, seg_opt), nw, nw * H, rule, nstates, s};
+    a.ragged_w = W;
+    if (rule_stream_grid(a.plan) > 0x7fffffff) return hipErrorInvalidValue;
+    switch (gen_planes(nstates)) {
+        case 1: return launch_p_ragged<1>(a);
+        case 2: return launch_p_ragged<2>(a);
+        case 3: return launch_p_ragged<3>(a);
     }
     return hipErrorInvalidValue;
 }

@@ -114,6 +114,10 @@ int rule_stream_largest_k(int64_t n);
 int rule_stream_max_k(int ilv);  // the deepest pass a layout runs by default
 hipError_t launch_rule_stream(const uint32_t* src, uint32_t* dst, int64_t W, int64_t H, int64_t pitch, int ilv, int k,
                               bool bounded, uint32_t rule, int64_t seg_opt, hipStream_t s);
+// ... on the whole-word scratch rows of a ragged byte board W cells wide (W >= 64, W % 32 != 0): src and
+// dst hold H rows of ceil(W / 32) words (launch_pack_ragged at that pitch), pad bits zero before and after
+hipError_t launch_rule_stream_ragged(const uint32_t* src, uint32_t* dst, int64_t W, int64_t H, int k, bool bounded,
+                                     uint32_t rule, int64_t seg_opt, hipStream_t s);
 
 // ---- gol_gen_stream.hip: the multi-plane streaming pass (Generations rules, nstates 3..8, packed boards of any size and
 // layout; gol_rule_stream's plan).  src / dst: the alive plane; dsrc / ddst: the gen_planes(nstates) decay planes, plane
@@ -121,6 +125,10 @@ hipError_t launch_rule_stream(const uint32_t* src, uint32_t* dst, int64_t W, int
 hipError_t launch_gen_stream(const uint32_t* src, uint32_t* dst, const uint32_t* dsrc, uint32_t* ddst, int64_t W,
                              int64_t H, int64_t pitch, int ilv, int k, bool bounded, uint32_t rule, int nstates,
                              int64_t seg_opt, hipStream_t s);
+// ... on scratch rows of a ragged byte board: every plane H rows of ceil(W / 32) words, decay plane k at + k * that
+hipError_t launch_gen_stream_ragged(const uint32_t* src, uint32_t* dst, const uint32_t* dsrc, uint32_t* ddst, int64_t W,
+                                    int64_t H, int k, bool bounded, uint32_t rule, int nstates, int64_t seg_opt,
+                                    hipStream_t s);
 
 // ---- gol_formats.hip
 // A board handle's Generations state (gol_board.h): the alive plane / alive bytes `board` and beside it `decay` -- packed
@@ -152,6 +160,12 @@ hipError_t launch_pack(const uint8_t* cells, uint32_t* words, int64_t W, int64_t
 hipError_t launch_pack_ragged(const uint8_t* cells, uint32_t* words, int64_t W, int64_t H, int64_t pitch, hipStream_t s);
 hipError_t launch_unpack_ragged(const uint32_t* words, uint8_t* cells, int64_t W, int64_t H, int64_t pitch,
                                 hipStream_t s);
+// the decay bytes of a ragged Generations byte board (d = state - 1 of a dying cell, else 0) <-> `planes` =
+// gen_planes(nstates) bit planes of such rows, plane k (bit k of d) at + k * pitch * H words, pad bits zero
+hipError_t launch_pack_ragged_decay(const uint8_t* decay, uint32_t* words, int64_t W, int64_t H, int64_t pitch,
+                                    int planes, hipStream_t s);
+hipError_t launch_unpack_ragged_decay(const uint32_t* words, uint8_t* decay, int64_t W, int64_t H, int64_t pitch,
+                                      int planes, hipStream_t s);
 hipError_t launch_unpack(const uint32_t* words, uint8_t* out, int64_t W, int64_t rows, int64_t pitch, int64_t row0,
                          int64_t stride, uint8_t value, int ilv, hipStream_t s);
 // Block rows of a ragged board (gol_formats.hip): aligned rows of ring_pitch(W, torus) words in layout ilv (1 or 2).

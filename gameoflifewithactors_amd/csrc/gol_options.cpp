@@ -76,6 +76,8 @@ const Option kOptions[] = {
          return set_any<&O::lanes_m>(b, v);
      }},
     {"view_stream", 0, get<&O::view_stream>, set_flag<&O::view_stream>},
+    {"rule_ragged", 0, get<&O::rule_ragged>,
+     [](gol_board* b, int64_t v) { return set_in(b->opt.rule_ragged, v, 0, 2, "rule_ragged must be 0, 1 (by size and call length) or 2"); }},
     // ---- test and A/B knobs (gol_debug.h)
     {"coop_epoch", kDebug, [](const gol_board* b) -> int64_t { return b->coop_epoch; },
      [](gol_board* b, int64_t v) {

@@ -283,6 +283,54 @@ int run_gen_stream(gol_board* b, int64_t gens) {
                      });
 }
 
+// The two passes on a ragged byte board's scratch rows: packed once -- ceil(W / 32) words per row, a
+// Generations board's decay planes behind the alive rows -- and kept there after the call (rag_state 1 / 4); the depths
+// and the remainder chain are those of the packed boards' passes above.
+int run_rule_ragged(gol_board* b, int64_t gens) {
+    const int64_t nw = (b->W + 31) / 32;
+    if (b->rag_state != 1) {
+        GOL_RC(ensure_rag(b, nw * b->H));
+        GOL_HIP(gol::launch_pack_ragged(b->cells(b->cur), b->rag[0], b->W, b->H, nw, b->stream));
+        b->rag_cur = 0;
+    }
+    b->rag_state = 1;
+    b->rag_pitch = nw;
+    const int cap = b->opt.rule_k ? b->opt.rule_k : gol::rule_stream_max_k(1);
+    return ping_pong(b, &b->rag_cur, gens,
+                     [cap](int64_t left) { return (int64_t)gol::rule_stream_largest_k(std::min<int64_t>(left, cap)); },
+                     [&](int64_t g) {
+                         GOL_HIP(gol::launch_rule_stream_ragged(b->rag[b->rag_cur], b->rag[b->rag_cur ^ 1], b->W, b->H,
+                                                                (int)g, b->boundary == GOL_BOUNDED, b->rule,
+                                                                b->opt.rule_seg_rows, b->stream));
+                         return GOL_OK;
+                     });
+}
+
+int run_gen_ragged(gol_board* b, int64_t gens) {
+    if (b->opt.rule_k == 8)
+        return fail(GOL_ERR_UNSUPPORTED, "rule_k 8: the multi-plane streaming pass of a Generations board runs 4, 2 or 1 "
+                                         "generations per pass");
+    const int64_t nw = (b->W + 31) / 32, plane = nw * b->H;
+    const int planes = gol::gen_planes(b->nstates);
+    if (b->rag_state != 4) {
+        GOL_RC(ensure_rag(b, plane * (1 + planes)));
+        GOL_HIP(gol::launch_pack_ragged(b->cells(b->cur), b->rag[0], b->W, b->H, nw, b->stream));
+        GOL_HIP(gol::launch_pack_ragged_decay(b->dec_cells(b->cur), b->rag[0] + plane, b->W, b->H, nw, planes, b->stream));
+        b->rag_cur = 0;
+    }
+    b->rag_state = 4;
+    b->rag_pitch = nw;
+    const int cap = b->opt.rule_k ? b->opt.rule_k : gol::gen_stream_max_k(1, planes, b->boundary == GOL_BOUNDED);
+    return ping_pong(b, &b->rag_cur, gens, [cap](int64_t left) { return (int64_t)gol::gen_stream_largest_k(left, cap); },
+                     [&](int64_t g) {
+                         uint32_t *src = b->rag[b->rag_cur], *dst = b->rag[b->rag_cur ^ 1];
+                         GOL_HIP(gol::launch_gen_stream_ragged(src, dst, src + plane, dst + plane, b->W, b->H, (int)g,
+                                                               b->boundary == GOL_BOUNDED, b->rule, b->nstates,
+                                                               b->opt.rule_seg_rows, b->stream));
+                         return GOL_OK;
+                     });
+}
+
 // Generations of the next streaming pass of a packed board with `left` to go, and that pass
 int stream_depth(const gol_board* b, int64_t left) {
     return gol::stream_largest_k(left, b->tblock, b->ilv, b->W / 32, b->boundary == GOL_BOUNDED);
@@ -301,7 +349,11 @@ int run_stream(gol_board* b, int64_t gens) {
 }
 
 // The scratch-row state (gol_board::rag_state) a pass leaves a ragged board in; every other pass needs the bytes.
-int rag_state_of(Pass p) { return p == Pass::StreamRagged ? 1 : (p == Pass::CoopRagged ? 2 : (p == Pass::Ring ? 3 : 0)); }
+int rag_state_of(Pass p) {
+    if (p == gol::kPassRuleRagged) return 1;  // the streaming pass's rows under another kernel
+    if (p == gol::kPassGenRagged) return 4;
+    return p == Pass::StreamRagged ? 1 : (p == Pass::CoopRagged ? 2 : (p == Pass::Ring ? 3 : 0));
+}
 
 int step_impl(gol_board* b, int64_t gens) {
     if (gens <= 0) return GOL_OK;
@@ -309,6 +361,8 @@ int step_impl(gol_board* b, int64_t gens) {
     b->last_pass = c.pass;
     if (b->rag_state != rag_state_of(c.pass)) GOL_RC(sync_bytes(b));
     if (c.pass == gol::kPassGenStream) return run_gen_stream(b, gens);
+    if (c.pass == gol::kPassRuleRagged) return run_rule_ragged(b, gens);
+    if (c.pass == gol::kPassGenRagged) return run_gen_ragged(b, gens);
     switch (c.pass) {
         case Pass::Multi: return b->multi->step(gens, &b->generation);
         case Pass::Wave: return run_wave(b, gens);

@@ -195,6 +195,29 @@ bool ring_by_size(int64_t W, int64_t H) { return W * H >= kRingMinCells; }
 bool use_ring(const gol_board* b) {
     return b->opt.ragged_ring == 2 || (b->opt.ragged_ring == 1 && ring_by_size(b->W, b->H));
 }
+// Ragged byte boards under another rule, life-like or Generations: the rule-generic and the multi-plane streaming pass
+// on the same ilv-1 whole-word scratch rows (gol_rule_stream_ragged / gol_gen_stream_ragged) in place
+// of the per-generation byte step, whatever the board's size (block rows under a rule do not exist).  The geometry
+// takes rows of at least 64 cells.  By default (option "rule_ragged" 1) on calls of at least kRuleRaggedMinGens
+// generations -- the pack launch in front of the pass costs a few byte steps -- and on boards above a size floor: the
+// byte step's time follows the cells, the streaming passes are latency-bound and flat up to a few million cells
+// (profiles/ragged_rules/ragged_rules_bench.json, us/generation at 64 per call, ragged / byte step):
+//   life-like (B36/S23)      1001^2 torus 6.0 / 6.2, bounded 5.4 / 7.5; 10001^2 10.5 / 334 and 10.5 / 490
+//   Generations (B2/S345/4)  1001^2 torus 7.5 / 6.6, bounded 5.6 / 7.8; 10001^2 14.8 / 367 and 13.7 / 705
+// Life-like rules keep the floor of the single-wave pass's 128 x 256 cells (every measured cell of >= 4 generations is
+// below the byte step with the state resident; with a pack in the call the 1001^2 torus is 16 % above it at 4
+// generations and 2 % at 16).  Generations boards lost on the 1001^2 torus at every call length, so their floor is
+// 2^22 cells: between the two measured sizes the byte step interpolates to 17 us there, the pass to under 13 with the
+// pack of a 4-generation call.  2 = every board and call the geometry takes (tests, A/B), 0 = never.
+constexpr int64_t kRuleRaggedMinGens = 4;
+constexpr int64_t kRuleRaggedMinCells = 128 * 256;
+constexpr int64_t kGenRaggedMinCells = (int64_t)1 << 22;
+bool use_rule_ragged(const gol_board* b, int64_t gens) {
+    if (b->packed || b->W % 32 == 0 || b->W < 64 || !b->opt.rule_ragged) return false;
+    if (b->opt.rule_ragged == 2) return true;
+    return b->W * b->H > (b->nstates > 2 ? kGenRaggedMinCells : kRuleRaggedMinCells) && gens >= kRuleRaggedMinGens;
+}
+
 int64_t ring_cells(int64_t W, int64_t H, int boundary) { return gol::ring_pitch(W, boundary == GOL_TORUS) * 32 * H; }
 
 int ring_ilv(const gol_board* b) { return ring_cells(b->W, b->H, b->boundary) < kSmallBoardCells ? 1 : 2; }
@@ -220,18 +243,21 @@ void board_layout(gol_board* b, int nparts, int tblock_k, int ilv) {
 // fails the ragged tests, and a byte board the lanes and cooperative ones, on their first compare.
 //
 // A board of the rule family (any rule but B3/S23, or the "rule_table" knob; gol_set_rule refuses multi-part boards)
-// has three passes: the single-wave kernel with the rule table where it applies, the rule-generic streaming pass
-// (gol_rule_step.hip) on every other packed board whatever its layout, and the per-generation byte step under the rule
-// on the byte boards left.  The lanes, cooperative, LDS-resident, ragged and pipelined passes are B3/S23 only.
+// has four passes: the single-wave kernel with the rule table where it applies, the rule-generic streaming pass
+// (gol_rule_step.hip) on every other packed board whatever its layout, the same pass on the scratch rows of the ragged
+// byte boards use_rule_ragged takes, and the per-generation byte step under the rule on the byte boards left.  The
+// lanes, cooperative, LDS-resident, pipelined and the other ragged passes are B3/S23 only.
 //
-// A Generations board (nstates > 2, gol_set_generations_rule; single boards only) has two passes whatever its rule
-// and size: the multi-plane streaming pass (gol_gen_stream.hip) on every packed board, and the per-generation byte step
-// on the (alive byte, d byte) pair on every byte board.  The single-wave pass is not taken there.
+// A Generations board (nstates > 2, gol_set_generations_rule; single boards only) has three passes whatever its rule:
+// the multi-plane streaming pass (gol_gen_stream.hip) on every packed board, the same pass on the scratch rows and decay
+// planes of the ragged byte boards use_rule_ragged takes, and the per-generation byte step on the (alive byte, d byte)
+// pair on the byte boards left.  The single-wave pass is not taken there.
 PassChoice choose_pass(const gol_board* b, int64_t gens) {
     if (b->multi) return {Pass::Multi, 0};
-    if (b->nstates > 2) return {b->packed ? kPassGenStream : Pass::Bytes, 0};
+    if (b->nstates > 2) return {b->packed ? kPassGenStream : (use_rule_ragged(b, gens) ? kPassGenRagged : Pass::Bytes), 0};
     if (use_wave_resident(b)) return {Pass::Wave, 0};
-    if (b->rule_family()) return {b->packed ? Pass::RuleStream : Pass::Bytes, 0};
+    if (b->rule_family())
+        return {b->packed ? Pass::RuleStream : (use_rule_ragged(b, gens) ? kPassRuleRagged : Pass::Bytes), 0};
     if (use_lanes(b, gens)) return {Pass::Lanes, 0};
     if (use_coop(b)) return {Pass::Coop, 0};
     int64_t rag_pitch = 0;

@@ -127,4 +127,81 @@ GOL_PLAN_HD int64_t rule_stream_grid(const RulePlan& p) {  // workgroups of kRul
     return (p.nwaves + kRuleWavesPerBlock - 1) / kRuleWavesPerBlock;
 }
 
+// ---- Ragged rows: a board of W cells per row, W >= 64 and not a multiple of 32, as rows of
+// nw = ceil(W / 32) consecutive words (blocks of one word), bit b of word j = cell 32 j + b, the W % 32 real cells of
+// the last word in its low bits and its pad bits ZERO.  The plan is rule_plan(nw, ...), the strips, segments, rows and
+// stored blocks are the functions above, and a lane is 32 consecutive cells of the ring of W cells at ring position
+// 32 (first_block + lane):
+//   torus    the lane's word is ring cells [q, q + 32), q = position mod W.  Where q is a multiple of 32 and the window
+//            ends inside the row that is word q / 32 as it stands; every other lane -- the halo lane left of word 0,
+//            the lane of the partial last word and all lanes to its right -- assembles it from up to three words: word
+//            q / 32 and the next shifted down by q % 32, and, where the window crosses the row's end after n < 32
+//            cells, word 0 shifted up by n (W >= 64: the window crosses the end at most once, and what follows it lies
+//            in word 0).  The zero pad bits are what lets the three parts be ORed together.
+//   bounded  a lane inside the row loads its word, the others nothing (rule_lane_load); the lane of the partial word
+//            keeps only its real cells alive at every level (rule_ragged_level_mask).
+//   stores   rule_lane_store's lanes; the lane of the partial word stores its real cells only (rule_ragged_store_mask),
+//            so pad bits stay zero from pass to pass.
+static constexpr int64_t kRuleRaggedMinWidth = 64;
+
+GOL_PLAN_HD int64_t rule_ragged_words(int64_t W) { return (W + 31) / 32; }
+
+GOL_PLAN_HD bool rule_ragged_ok(int64_t W) { return W >= kRuleRaggedMinWidth && W % 32 != 0; }
+
+GOL_PLAN_HD uint32_t rule_ragged_tail_mask(int64_t W) { return (1u << (uint32_t)(W % 32)) - 1u; }  // W % 32 != 0
+
+// The window of a torus lane: word `word`, with `second` also word + 1 (both in [0, nw)), and with seam < 32 word 0.
+struct RaggedWindow {
+    int64_t word;
+    int32_t shift;   // 0..31: the window starts at bit `shift` of `word`
+    int32_t second;  // 1: the window goes on in word + 1 (shift > 0, and `word` is not the row's last)
+    int32_t seam;    // cells of the window before the row's end, 1..31; 32 = the window does not cross it
+};
+
+GOL_PLAN_HD RaggedWindow rule_ragged_window(const RuleWave& w, int lane, int64_t W) {
+    const int64_t q = rule_mod(32 * (w.first_block + lane), W);
+    RaggedWindow g;
+    g.word = q / 32;
+    g.shift = (int32_t)(q % 32);
+    g.second = g.shift > 0 && g.word + 1 < rule_ragged_words(W);
+    g.seam = W - q < 32 ? (int32_t)(W - q) : 32;
+    return g;
+}
+GOL_PLAN_HD bool rule_ragged_plain(const RaggedWindow& g) { return g.shift == 0 && g.seam == 32; }
+
+// The lane's word from the words it read: a = row[word], b = row[word + 1] (if second, else anything), c = row[0] (if
+// seam < 32, else anything).
+GOL_PLAN_HD uint32_t rule_ragged_assemble(const RaggedWindow& g, uint32_t a, uint32_t b, uint32_t c) {
+    uint32_t v = a >> (uint32_t)g.shift;
+    if (g.second) v |= b << (32u - (uint32_t)g.shift);
+    if (g.seam < 32) v |= c << (uint32_t)g.seam;
+    return v;
+}
+
+// ... read from the row (nw words) itself
+GOL_PLAN_HD uint32_t rule_ragged_load(const uint32_t* row, const RaggedWindow& g) {
+    const uint32_t a = row[g.word];
+    const uint32_t b = g.second ? row[g.word + 1] : 0u;
+    const uint32_t c = g.seam < 32 ? row[0] : 0u;
+    return rule_ragged_assemble(g, a, b, c);
+}
+
+// The lane that holds the row's partial last word (as a block of the row, before any modulo)
+GOL_PLAN_HD bool rule_ragged_partial(const RulePlan& p, const RuleWave& w, int lane) {
+    return w.first_block + lane == p.nblocks - 1;
+}
+
+// What a storing lane (rule_lane_store) writes of its word: the real cells
+GOL_PLAN_HD uint32_t rule_ragged_store_mask(const RulePlan& p, const RuleWave& w, int lane, int64_t W) {
+    return rule_ragged_partial(p, w, lane) ? rule_ragged_tail_mask(W) : 0xffffffffu;
+}
+
+// Bounded boards: the cells of the lane's word that may live, ANDed into every level's output (in rows inside the
+// board): none outside the row, the real cells of the partial word, else all.
+GOL_PLAN_HD uint32_t rule_ragged_level_mask(const RulePlan& p, const RuleWave& w, int lane, int64_t W) {
+    const int64_t raw = w.first_block + lane;
+    if (raw < 0 || raw >= p.nblocks) return 0u;
+    return raw == p.nblocks - 1 ? rule_ragged_tail_mask(W) : 0xffffffffu;
+}
+
 }  // namespace gol

@@ -22,6 +22,9 @@
 // Torus: every lane loads block index mod blocks-per-row and row index mod H.  Bounded: blocks and rows outside the
 // board load nothing (zero) and are forced dead at EVERY level -- under a rule with birth bit 0 a dead cell with no
 // live neighbour comes alive, outside the board too, unless it is masked.
+//
+// gol_rule_stream_ragged below is the same pass on the whole-word scratch rows of a ragged byte board (width not a
+// multiple of 32; gol_policy.cpp use_rule_ragged).
 #include "gol_internal.h"
 #include "gol_bitlogic.h"
 #include "gol_layout.h"
@@ -207,6 +210,97 @@ __global__ __launch_bounds__(64 * kRuleWavesPerBlock) void gol_rule_stream(const
     }
 }
 
+// gol_rule_stream at M = 1 on the scratch rows of a ragged byte board W cells wide: rows of plan.nblocks = pitch =
+// ceil(W / 32) words, the last one partial with zero pad bits (gol_rule_plan.h "Ragged rows").  Only what
+// a lane loads, the level mask of the partial word's lane and what that lane stores differ; the windows, the DPP edges
+// and the levels do not know.  Torus: a lane whose 32 ring cells are not one whole word of the row assembles them from
+// up to three (rule_ragged_load), and only in the waves that hold such a lane -- `shifted` is wave-uniform, so every
+// other wave of a wide board runs the aligned pass's one load per row.  A kernel of its own beside gol_rule_stream, not
+// a template value of it: a body shared through a function changed how the compiler reads the plan out of the kernel
+// arguments, in every instantiation of the aligned kernel.
+template <int K, bool BOUNDED>
+__global__ __launch_bounds__(64 * kRuleWavesPerBlock) void gol_rule_stream_ragged(const uint32_t* __restrict__ src,
+                                                                                  uint32_t* __restrict__ dst,
+                                                                                  RulePlan plan, int64_t pitch,
+                                                                                  uint32_t rule, int64_t W) {
+    constexpr int M = 1;
+    const int lane = threadIdx.x & 63;
+    const int64_t wave =
+        (int64_t)blockIdx.x * kRuleWavesPerBlock + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (wave >= plan.nwaves) return;
+    const RuleWave w = rule_wave(plan, wave);
+    int64_t lblk, sblk;
+    const bool lane_ld = rule_lane_load(plan, w, lane, &lblk) || !BOUNDED;  // (a torus lane always loads)
+    const bool lane_st = rule_lane_store(plan, w, lane, &sblk);
+    // bounded: the cells of the lane's word that may live; torus: the lane's window on the ring of W cells
+    const uint32_t lanemask = BOUNDED ? rule_ragged_level_mask(plan, w, lane, W) : 0xffffffffu;
+    const uint32_t stmask = rule_ragged_store_mask(plan, w, lane, W);
+    RaggedWindow rw{};     // torus only: the lane's window, and whether any lane of this wave assembles its word
+    bool shifted = false;  // (wave-uniform)
+    if constexpr (!BOUNDED) {
+        rw = rule_ragged_window(w, lane, W);
+        shifted = __ballot(!rule_ragged_plain(rw)) != 0;
+    }
+    const int64_t H = plan.H;
+    const int64_t ybase = w.r0 - K;  // the row step 0 loads, before the modulo
+
+    // step t's row: loaded only inside the stream, (bounded) inside the board and by lanes inside the board
+    int64_t ywrap = BOUNDED ? ybase : rule_mod(ybase, H);  // the next row to load (torus: wrapped)
+    auto load_row = [&](int64_t t, uint32_t (&v)[M]) {
+#pragma unroll
+        for (int j = 0; j < M; j++) v[j] = 0;
+        const bool row_ok = t < w.steps && (!BOUNDED || (ywrap >= 0 && ywrap < H));
+        if constexpr (BOUNDED) {
+            if (row_ok && lane_ld) v[0] = src[ywrap * pitch + lblk];
+        } else {
+            if (row_ok) v[0] = shifted ? rule_ragged_load(src + ywrap * pitch, rw) : src[ywrap * pitch + rw.word];
+        }
+        ywrap++;
+        if (!BOUNDED && ywrap == H) ywrap = 0;
+    };
+
+    RuleWindows<K, M, BOUNDED> win;
+    win.clear();
+    uint32_t nxt[kRuleTripRows][M];
+#pragma unroll
+    for (int r = 0; r < kRuleTripRows; r++) load_row(r, nxt[r]);
+
+    const int64_t nstore = w.r1 - w.r0;
+#pragma nounroll
+    for (int64_t T = 0; T < w.trips; T++) {
+        uint32_t cur[kRuleTripRows][M];
+#pragma unroll
+        for (int r = 0; r < kRuleTripRows; r++)
+#pragma unroll
+            for (int j = 0; j < M; j++) cur[r][j] = nxt[r][j];
+        const int64_t t0 = T * kRuleTripRows;
+#pragma unroll
+        for (int r = 0; r < kRuleTripRows; r++) load_row(t0 + kRuleTripRows + r, nxt[r]);
+        __builtin_amdgcn_sched_barrier(0);  // the prefetch stays at the top of the trip
+        auto finish = [&](int64_t t, uint32_t (&x)[M]) {  // the last level's output of step t is row r0 - 2 K + t
+            const int64_t o = t - 2 * K;
+            if (o >= 0 && o < nstore && lane_st) dst[(w.r0 + o) * pitch + sblk] = x[0] & stmask;
+        };
+        win.template step<0>(cur[0], rule, lanemask, ybase + t0 - 1, H);
+        finish(t0, cur[0]);
+        win.template step<1>(cur[1], rule, lanemask, ybase + t0, H);
+        finish(t0 + 1, cur[1]);
+        win.template step<2>(cur[2], rule, lanemask, ybase + t0 + 1, H);
+        finish(t0 + 2, cur[2]);
+    }
+}
+
+template <int K>
+hipError_t launch_k_ragged(const uint32_t* src, uint32_t* dst, const RulePlan& plan, int64_t W, uint32_t rule,
+                           hipStream_t s) {
+    const dim3 grid((unsigned)rule_stream_grid(plan)), block(64 * kRuleWavesPerBlock);
+    if (plan.bounded)
+        hipLaunchKernelGGL((gol_rule_stream_ragged<K, true>), grid, block, 0, s, src, dst, plan, plan.nblocks, rule, W);
+    else
+        hipLaunchKernelGGL((gol_rule_stream_ragged<K, false>), grid, block, 0, s, src, dst, plan, plan.nblocks, rule, W);
+    return hipGetLastError();
+}
+
 template <int K, int M>
 hipError_t launch_km(const uint32_t* src, uint32_t* dst, const RulePlan& plan, int64_t pitch, uint32_t rule,
                      hipStream_t s) {
@@ -264,6 +358,27 @@ hipError_t launch_rule_stream(const uint32_t* src, uint32_t* dst, int64_t W, int
         case 1: return launch_m<1>(src, dst, plan, pitch, rule, s);
         case 2: return launch_m<2>(src, dst, plan, pitch, rule, s);
         case 4: return launch_m<4>(src, dst, plan, pitch, rule, s);
+    }
+    return hipErrorInvalidValue;
+}
+
+// The plan of a pass over the scratch rows of a ragged board (ceil(W / 32) words per row): rule_stream_plan's targets
+RulePlan rule_stream_plan_ragged(int64_t W, int64_t H, int k, bool bounded, int64_t seg_opt) {
+    return rule_stream_plan(rule_ragged_words(W) * 32, H, 1, k, bounded, seg_opt);
+}
+
+// k generations on the scratch rows of a ragged byte board: src and dst hold H rows of ceil(W / 32) words, pad bits zero
+hipError_t launch_rule_stream_ragged(const uint32_t* src, uint32_t* dst, int64_t W, int64_t H, int k, bool bounded,
+                                     uint32_t rule, int64_t seg_opt, hipStream_t s) {
+    if (!rule_ragged_ok(W) || H < 1 || !rule_packed_ok(rule) || rule_stream_largest_k(k) != k)
+        return hipErrorInvalidValue;
+    const RulePlan plan = rule_stream_plan_ragged(W, H, k, bounded, seg_opt);
+    if (rule_stream_grid(plan) > 0x7fffffff) return hipErrorInvalidValue;
+    switch (k) {
+        case 8: return launch_k_ragged<8>(src, dst, plan, W, rule, s);
+        case 4: return launch_k_ragged<4>(src, dst, plan, W, rule, s);
+        case 2: return launch_k_ragged<2>(src, dst, plan, W, rule, s);
+        case 1: return launch_k_ragged<1>(src, dst, plan, W, rule, s);
     }
     return hipErrorInvalidValue;
 }

@@ -233,6 +233,11 @@ int gol_pass_timing(gol_board* b, int n, double* interior_us, double* wait_us, d
  *   "lanes_m" 0 | 3 | 5 | 9 | 17 its words per lane and half-row (0: 3 up to 1024 columns, else 9 when W % 512 == 0)
  *   "view_stream" 1 | 0          views (gol_view_counts / gol_render_view) of packed boards with scale >= 16 * ilv on the
  *                                streaming kernel (0: every view on the per-pixel kernel, the library's cross-check)
+ *   "rule_ragged" 1 | 2 | 0      ragged boards (width not a multiple of 32, at least 64) under another rule, life-like or
+ *                                Generations: the streaming passes on whole-word scratch rows in place of the
+ *                                per-generation byte step -- on boards of more than 128 x 256 cells
+ *                                (Generations rules: 2^22 cells) and calls of at least 4 generations (1), on every
+ *                                such board and call (2), or never (0)
  * Unknown names and out-of-range values return GOL_ERR_INVALID.  Results are bit-identical for every setting.
  * (Test and A/B knobs -- spin limits, tag epochs, launch API -- are not board options: they live behind
  * gol_debug_set_option in the library's internal header csrc/gol_debug.h.)
